@@ -22,23 +22,28 @@ fp16 forward to 2e-2 of the reference's float32 output and the float32 forward t
     none                 no network: the float32 prediction is a synthetic INPUT, only the per-pixel path is timed
 `--config` presets: c2 (dpt_hybrid_384, batch 1, 512x512: latency), c3 (default), c3match (config 3 with NET_SIZE_MATCH:
 net 1024, 4097 tokens), c4 (Boost on one 4K image), c5 (dav2_vitl on 1920x1080 frames, 2443 tokens).  c3 is the metric's line;
-the default invocation ALSO runs short legs of c5, c2 and c4 (sub-processes, after the timed region) and carries their digests
-under `other_configs`, so that the driver's one line holds four driver-timed configurations.
+with --full the default invocation ALSO runs short legs of c5, c2, c3match and c4 (sub-processes, after the timed region) and
+carries their digests under `other_configs`, so that one line holds the driver-timed configurations.
 
-Contract: `python bench.py --gpus N --steps K --warmup W`.  For N > 1 the driver launches one rank per GPU with
+Contract: `python bench.py --gpus N --steps K --warmup W`.  A plain run sets up, warms up, times the K steps and prints ONE JSON
+line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = wall milliseconds of one timed step, ...).  Everything
+else it can measure or check -- rooflines, per-kernel timings, outputs_sha256, gather_check, route_check, the funnel leg, the CPU
+baseline, the other configurations -- runs only with `--full`, after the timed region.  `--dump-outputs DIR` writes what the
+last timed step computed (stereo pair, uint16 depth, normal map) as DIR/<name>.npy (benchlib/outputs.py); the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.  For N > 1 the driver launches one rank per GPU with
 torch.distributed.run; run WITHOUT a launcher (`python bench.py --gpus 8`), bench.py launches the N ranks itself (the same
 torch.distributed.run command, rendezvous on 127.0.0.1) and rank 0's line is the output.  Units are sharded across ranks (weak
 scaling: every rank renders its own batch, no data-path collective) and the collated outputs (stereo pair + uint16 depth + normal
 map, packed into one byte buffer) are gathered to rank 0 with ONE RCCL gather per step, overlapped with the next step's kernels
-(--no-gather to leave it out); after the timed region rank 0 re-renders the LAST rank's units itself and compares them with the
-gathered bytes (`gather_check`).  Rank 0 prints ONE JSON line; on one GPU the metric's config also carries
-`funnel`: the same batch through the drop-in boundary (core_generation_funnel, PIL in -> PIL out), reported beside `value`,
-never as it.
+(--no-gather to leave it out); with --full, after the timed region rank 0 re-renders the LAST rank's units itself and compares
+them with the gathered bytes (`gather_check`).  Rank 0 prints ONE JSON line; with --full on one GPU the metric's
+config also carries `funnel`: the same batch through the drop-in boundary (core_generation_funnel, PIL in -> PIL out), reported
+beside `value`, never as it (`--funnel` asks for it alone).
 
-`roofline` is the dominant in-tree kernel of the step by its time INSIDE the timed region: the C ABI brackets its launches with
-HIP events on the launch stream while the steps are timed (ds_kernel_timer_enable, include/depthstereo.h), `achieved` = algorithmic
-flops per launch / that average duration.  The microbenchmark of the same launch shape on randn operands is the side note
-(`microbenchmark`), not the figure.
+`roofline` (--full) is the dominant in-tree kernel of the step by its time inside the step: the C ABI brackets its launches with
+HIP events on the launch stream in an instrumented repeat of the timed steps (ds_kernel_timer_enable, include/depthstereo.h),
+`achieved` = algorithmic flops per launch / that average duration.  The microbenchmark of the same launch shape on randn operands
+is the side note (`microbenchmark`), not the figure.
 """
 import argparse
 import contextlib
@@ -60,12 +65,15 @@ import numpy as np  # noqa: E402
 from benchlib import workload as wl  # noqa: E402
 from benchlib.launch import compare_gathered, dist_setup, launch_command, max_over_ranks, self_launch, selftest_launch  # noqa: E402,F401
 from benchlib.legs import funnel_leg, other_configs_leg, route_check_leg  # noqa: E402
+from benchlib.outputs import dump_outputs  # noqa: E402
 from benchlib.profiles import traffic_from_profile, valu_from_profile  # noqa: E402
 from benchlib.rooflines import (HBM_COPY_GBPS, HBM_PEAK_GBPS, IN_STEP, MICRO, encoder_rooflines, mfma_roofline,  # noqa: E402,F401
                                 microbench_conv)
 from benchlib.workload import (algo_bytes_normalmap, algo_bytes_stereo, build_model, cpu_baseline, default_net_size, net_grid,  # noqa: E402,F401
                                run_forward, synth_batch)
 
+T_START = time.perf_counter()
+FULL_WALL_S = 540.0               # --full: the other configurations' legs end within 9 minutes of the start (benchlib.legs)
 H = W = 1024                      # frame size of the run (mirrors benchlib.workload's state: run_pipeline / run_c4 set both)
 DEPTH_KIND = "steps"
 
@@ -93,17 +101,17 @@ def parse_args(argv=None):
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: do not gather the collated outputs to rank 0")
     ap.add_argument("--funnel", action="store_true", help="also time the drop-in funnel (PIL in -> PIL out) on the same batch "
-                                                        "(default for the metric's config c3 on one GPU; reported beside `value`, never as it)")
+                                                        "(with --full: default for the metric's config c3 on one GPU; reported beside `value`, never as it)")
     ap.add_argument("--no-funnel", action="store_true")
     ap.add_argument("--depth", default="steps", choices=["steps", "smooth"],
                     help="--model none only: synthetic prediction with steps + occluders (default), or smooth only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-route-check", action="store_true", help="leave out the untimed route check (profile runs: its library-routed "
                                                                   "forward would show up in the kernel statistics of the step)")
-    ap.add_argument("--timers-in-region", action="store_true", help="record the kernel timers' events inside the timed region (rounds 3-5; costs ~2 ms per step)")
+    ap.add_argument("--timers-in-region", action="store_true", help="--full: record the kernel timers' events inside the timed region (rounds 3-5; costs ~2 ms per step)")
     ap.add_argument("--no-kernel-timers", action="store_true", help="do not bracket the kernels with events inside the timed region (A/B of the "
                                                                     "timers' own cost; the rooflines then fall back to the microbenchmarks)")
-    ap.add_argument("--no-other-configs", action="store_true", help="default invocation only: skip the short c5 / c2 / c4 legs behind the metric's line")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full, default invocation only: skip the short c5 / c2 / c4 legs behind the metric's line")
     ap.add_argument("--other-configs-timeout", type=float, default=240.0, help="seconds per other-config leg (c4: twice that)")
     ap.add_argument("--no-micro", action="store_true", help="skip the microbenchmarks beside the in-step rooflines (profile runs)")
     ap.add_argument("--selftest-launch", action="store_true", help="CPU / gloo: exercise the launcher + gather plumbing without a GPU (tests)")
@@ -114,6 +122,13 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="minimum wall time of the CPU baseline leg")
     ap.add_argument("--cpu-python-unit", type=int, default=512, help="side of the one unit timed through the pure-Python port (0 = skip)")
     ap.add_argument("--boost-rmax", type=int, default=1600, help="c4: Boost's whole-image size limit (standalone default 1600, paper 3000)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: rooflines (kernel timers, microbenchmarks), per-kernel timings, "
+                         "outputs_sha256, gather_check, route_check, the funnel leg, the CPU baseline and (default config) the other "
+                         "configurations; a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "under 64 MB in all: a fixed seeded sample of image rows when larger; benchlib/outputs.py)")
     return ap.parse_args(argv)
 
 
@@ -193,7 +208,7 @@ def run_pipeline(args):
     img_np, pred_np = shard(rank)
     img = torch.from_numpy(img_np).to(dev)
     pred_in = torch.from_numpy(pred_np).to(dev)
-    nat.profile_enable(local_rank, True)
+    full = args.full
     model, minfo = (None, None)
     if model_name != "none":
         from src import gemm_tuning
@@ -285,20 +300,25 @@ def run_pipeline(args):
     # round6_timers_ab.txt) -- every record is a barrier packet between two kernels.  So the timed region runs WITHOUT them, and the
     # roofline durations come from an instrumented repeat of the same steps right behind it (same process, tensors, launches and
     # clocks; its own step time is reported as instrumented_ms_per_step).  --timers-in-region restores the old arrangement (A/B).
-    timers_on = model is not None and not args.no_kernel_timers
+    # A plain run (no --full) times the steps and nothing else.
+    timers_on = full and model is not None and not args.no_kernel_timers
     if timers_on and args.timers_in_region:
         nat.kernel_timer_enable(local_rank, True)
     if world > 1:
         dist.barrier()
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step() if args.steps > 0 else None
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and last is not None:                     # (step() returns stereo pair, normal map, depth)
+        dump_outputs(args.dump_outputs, dict(zip(("stereo_pair", "normal_map", "depth_u16"), last)))
+    del last
     instrumented_ms = None
     if timers_on and not args.timers_in_region:
         n_inst = min(args.steps, 20)                             # the event rings hold 1024 launches per kernel kind
@@ -325,7 +345,9 @@ def run_pipeline(args):
     # measurement): k_polylines via HIP events recorded inside the C ABI on the launch stream, ds_normalmap via events on torch's
     # current stream (which IS the launch stream of the ctypes call)
     render_ms, exact_ms, nm_ms = [], [], []
-    for _ in range(min(args.steps, 5)):
+    if full:
+        nat.profile_enable(local_rank, True)
+    for _ in range(min(args.steps, 5) if full else 0):
         _, _, d16 = step()
         torch.cuda.synchronize()
         r, e = nat.profile_last_ms(local_rank)
@@ -338,12 +360,12 @@ def run_pipeline(args):
             e1.record()
             e1.synchronize()
             nm_ms.append(e0.elapsed_time(e1))
-    exact_rows, general_px = nat.last_stats(img)
+    exact_rows, general_px = nat.last_stats(img) if full else (None, None)
 
     # gather_check (N > 1, untimed): rank 0 renders the LAST rank's units itself (its inputs are a function of the rank) and compares
     # them with the bytes that rank sent through the gather in the last step
     gather_check = None
-    if gather_ok and rank == 0:
+    if full and gather_ok and rank == 0:
         torch.cuda.synchronize()
         side.synchronize()
         o_img_np, o_pred_np = shard(world - 1)
@@ -373,7 +395,7 @@ def run_pipeline(args):
     # -- strong scaling: of ALL units in rank order, i.e. the same digest on 1 / 2 / 4 / 8 GPUs ("outputs must be byte-identical
     # across GPU counts"); weak scaling: of rank 0's units, whose inputs do not depend on the number of ranks either
     outputs_sha256 = None
-    if rank == 0:
+    if full and rank == 0:
         import hashlib
         hsh = hashlib.sha256()
         if gather_ok and strong:
@@ -389,12 +411,12 @@ def run_pipeline(args):
             del o_sbs, o_nmap, o_d16, own
         outputs_sha256 = {"sha256": hsh.hexdigest(), "of": ("all units of the job, rank order" if (gather_ok and strong) else "the units of rank 0"),
                           "units": (global_batch if (gather_ok and strong) else batch)}
-    elif world > 1 and not (gather_ok and strong):
+    elif full and world > 1 and not (gather_ok and strong):
         step()                                                  # (the ranks stay in step with rank 0's extra render: its gather is collective)
         torch.cuda.synchronize()
 
     roofs, conv_roof = {}, None
-    if model is not None:
+    if full and model is not None:
         if args.no_micro:
             roofs = {}
             for kind, (n, ms) in timed.items():
@@ -415,11 +437,11 @@ def run_pipeline(args):
     torch.cuda.synchronize()
 
     route = None
-    if model is not None and not args.no_route_check:
+    if full and model is not None and not args.no_route_check:
         route = route_check_leg(nat, vm, model, model_name, img, batch, net_size, net_h)
 
     funnel = None
-    want_funnel = args.funnel or (default_invocation and world == 1)
+    want_funnel = args.funnel or (full and default_invocation and world == 1)
     if want_funnel and not args.no_funnel and rank == 0 and model is not None:
         funnel = funnel_leg(model, model_name, img_np, net_size, net_h, normalmap)
 
@@ -427,21 +449,23 @@ def run_pipeline(args):
 
     if rank == 0:
         units = batch * world * args.steps
-        avg_render_s = float(np.mean(render_ms)) * 1e-3
-        achieved = batch * algo_bytes_stereo() / avg_render_s / 1e9
-        stereo_roof = {"bound": "hbm", "kernel": "k_polylines", "achieved": achieved, "peak": HBM_PEAK_GBPS,
-                       "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": None,
-                       "traffic_from_profile": traffic_from_profile("k_polylines<", batch) if (H, W) == (1024, 1024) else None,
-                       "traffic_general_pass_from_profile": traffic_from_profile("k_polylines_general", batch) if (H, W) == (1024, 1024) else None,
-                       "source": "HIP events inside the C ABI around k_polylines + k_polylines_general, in the step, on the network's own depth",
-                       "algorithmic_bytes_per_launch": batch * algo_bytes_stereo(),
-                       "avg_kernel_ms": float(np.mean(render_ms)), "exact_fallback_ms": float(np.mean(exact_ms)),
-                       "exact_fallback_rows": exact_rows, "general_pixels": general_px,
-                       # what actually bounds it: float64 VALU issue (bit-exactness forces binary64 in the reference's order)
-                       "fp64_valu": {"peak_tflops": 78.6, "note": "see DESIGN.md 3.1: instruction count per 64 pixel-eyes from "
-                                                                  "the committed PMC profile",
-                                     "main_kernel": valu_from_profile("k_polylines<", batch) if (H, W) == (1024, 1024) else None,
-                                     "general_pass": valu_from_profile("k_polylines_general", batch) if (H, W) == (1024, 1024) else None}}
+        stereo_roof = None
+        if render_ms:                                            # (--full: the per-kernel passes above)
+            avg_render_s = float(np.mean(render_ms)) * 1e-3
+            achieved = batch * algo_bytes_stereo() / avg_render_s / 1e9
+            stereo_roof = {"bound": "hbm", "kernel": "k_polylines", "achieved": achieved, "peak": HBM_PEAK_GBPS,
+                           "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": None,
+                           "traffic_from_profile": traffic_from_profile("k_polylines<", batch) if (H, W) == (1024, 1024) else None,
+                           "traffic_general_pass_from_profile": traffic_from_profile("k_polylines_general", batch) if (H, W) == (1024, 1024) else None,
+                           "source": "HIP events inside the C ABI around k_polylines + k_polylines_general, in the step, on the network's own depth",
+                           "algorithmic_bytes_per_launch": batch * algo_bytes_stereo(),
+                           "avg_kernel_ms": float(np.mean(render_ms)), "exact_fallback_ms": float(np.mean(exact_ms)),
+                           "exact_fallback_rows": exact_rows, "general_pixels": general_px,
+                           # what actually bounds it: float64 VALU issue (bit-exactness forces binary64 in the reference's order)
+                           "fp64_valu": {"peak_tflops": 78.6, "note": "see DESIGN.md 3.1: instruction count per 64 pixel-eyes from "
+                                                                      "the committed PMC profile",
+                                         "main_kernel": valu_from_profile("k_polylines<", batch) if (H, W) == (1024, 1024) else None,
+                                         "general_pass": valu_from_profile("k_polylines_general", batch) if (H, W) == (1024, 1024) else None}}
         wl_text = (f"{minfo['name']} forward (fp16, random-init weights seed {minfo['init_seed']}, net {minfo['net']}, "
               f"{minfo['tokens']} tokens) + " if model is not None else "")
         out = {
@@ -473,10 +497,11 @@ def run_pipeline(args):
                                       + (", ONE RCCL gather of the collated outputs (stereo pair + uint16 depth"
                                          + (" + normal map" if normalmap else "") + f", {unit_bytes} bytes per unit) to rank 0 per step, overlapped"
                                          if gather_ok else "")},
+        }
+        if stereo_roof is not None:
             # the dominant hand-written kernel of the step by its time INSIDE the timed region (in-step launches x average duration);
             # the others follow under their own keys; with no network it is the stereo kernel
-            "roofline": stereo_roof,
-        }
+            out["roofline"] = stereo_roof
         if roofs and not args.no_micro:
             out["roofline"] = max(roofs.values(), key=lambda r: r["avg_kernel_ms"] * r["launches_per_step"])
             for kind, key in (("attention", "roofline_attention"), ("linear_gelu", "roofline_linear"), ("linear_residual", "roofline_linear_residual")):
@@ -511,19 +536,20 @@ def run_pipeline(args):
                     r["frac_of_measured_copy_peak"] = r["achieved"] / HBM_COPY_GBPS
         if gather_check is not None:
             out["gather_check"] = gather_check
-        out["outputs_sha256"] = outputs_sha256
+        if full:
+            out["outputs_sha256"] = outputs_sha256
         if route is not None:
             out["route_check"] = route
         if funnel is not None:
             out["funnel"] = funnel
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(model_name, net_size, net_h, args.cpu_sample, seed=1000, min_seconds=args.cpu_seconds,
                                                normalmap=normalmap, python_unit=args.cpu_python_unit,
                                                init_seed=minfo["init_seed"] if minfo else 0)
-        if default_invocation and world == 1 and not args.no_other_configs:
+        if full and default_invocation and world == 1 and not args.no_other_configs:
             # the other BASELINE configurations, driver-timed in the same command (sub-processes; the parent's GPU work is done)
             torch.cuda.empty_cache()
-            out["other_configs"] = other_configs_leg(args.other_configs_timeout)
+            out["other_configs"] = other_configs_leg(args.other_configs_timeout, deadline=T_START + FULL_WALL_S)
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
@@ -571,7 +597,7 @@ def run_c4(args):
         d16 = nat.depth_to_u16(pred.unsqueeze(0), True)                # LeReS is a near-is-dark model (inverted)
         sbs = sg.create_stereoimages_batch(img.unsqueeze(0), d16, 2.5, 0.0, ['left-right'], 0.0, 1.0, args.fill)[0]
         nm = nmg.create_normalmap_batch(d16) if not args.no_normalmap else None
-        return sbs, nm
+        return sbs, nm, d16
 
     # algorithmic flops of one image: every convolution of the two networks, counted by hooks during the (untimed) priming step
     flops = [0.0]
@@ -605,13 +631,17 @@ def run_c4(args):
         dist.barrier()
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step() if args.steps > 0 else None
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
         torch.cuda.synchronize()
     elapsed = max_over_ranks(time.perf_counter() - t0, world, dev)
+    if args.dump_outputs and rank == 0 and last is not None:                     # (rank 0 holds the image's results)
+        dump_outputs(args.dump_outputs, dict(zip(("stereo_pair", "normal_map", "depth_u16"), last)))
+    del last
     fl = torch.tensor([flops[0]], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(fl, op=dist.ReduceOp.SUM)

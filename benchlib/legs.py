@@ -34,11 +34,12 @@ def route_check_leg(nat, vm, model, model_name, img, batch, net_size, net_h):
             "c_abi_calls_per_forward": calls}
 
 
-def other_configs_leg(timeout_s):
-    """Short legs of the other BASELINE configurations, each in a sub-process of its own after the timed region (a leg that fails or
-    hangs costs its timeout, never the line): c5 (8 steps = 64 frames), c2 (20 hipGraph replays), c3match (3 steps), c4 (1 image, at
-    r_max 1600 and 3000).  A digest of each leg's own JSON
-    line -- value, ms per step, workload, roofline -- goes under `other_configs`."""
+def other_configs_leg(timeout_s, deadline=None):
+    """Short legs of the other BASELINE configurations, each `bench.py --full` in a sub-process of its own after the timed region (a
+    leg that fails or hangs costs its timeout, never the line): c5 (8 steps = 64 frames), c2 (20 hipGraph replays), c3match (3 steps),
+    c4 (1 image, at r_max 1600 and 3000).  A digest of each leg's own JSON
+    line -- value, ms per step, workload, roofline -- goes under `other_configs`.  No leg runs past `deadline` (time.perf_counter()),
+    and none starts after a leg has failed: a failed leg may have left the GPU in a bad state."""
     # c5 with --overlap: its per-pixel passes (the polylines fallbacks of a network's noisy 1080p prediction: one or two workgroups
     # sweeping flagged rows for ~5 ms, a VALU-bound general pass) run on a second stream beside the next frames' forward (round 6:
     # 190 -> 223 pairs/s on one box; on c3 the same switch buys nothing: 793 vs 781); 8 steps = 64 frames.  c3match = SURVEY 8(d)'s
@@ -53,8 +54,16 @@ def other_configs_leg(timeout_s):
             ("c4", ["--config", "c4", "--steps", "1", "--warmup", "0"], 2 * timeout_s, None),
             ("c4_rmax3000", ["--config", "c4", "--steps", "1", "--warmup", "0", "--boost-rmax", "3000"], 2 * timeout_s, None)]
     out = {}
+    stop = None
     for name, extra, limit, env_extra in legs:
-        cmd = [sys.executable, BENCH_PY] + extra + ["--no-cpu-baseline", "--no-route-check", "--no-funnel", "--no-other-configs"]
+        if deadline is not None and stop is None and deadline - time.perf_counter() < 30:
+            stop = "the wall budget of the --full command is spent"
+        if stop is not None:
+            out[name] = {"error": f"not run: {stop}", "seconds": 0.0}
+            continue
+        if deadline is not None:
+            limit = min(limit, deadline - time.perf_counter())
+        cmd = [sys.executable, BENCH_PY, "--full"] + extra + ["--no-cpu-baseline", "--no-route-check", "--no-funnel", "--no-other-configs"]
         env = dict(os.environ)
         env.update({k: v for k, v in (env_extra or {}).items() if k not in os.environ})          # (the caller's own setting wins)
         t0 = time.perf_counter()
@@ -63,6 +72,7 @@ def other_configs_leg(timeout_s):
             line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
             if p.returncode != 0 or not line:
                 out[name] = {"error": f"exit code {p.returncode}", "stderr_tail": p.stderr[-400:], "seconds": time.perf_counter() - t0}
+                stop = f"leg {name} failed"
                 continue
             j = json.loads(line[-1])
             roof = j.get("roofline") or {}
@@ -71,12 +81,14 @@ def other_configs_leg(timeout_s):
                          "workload": (j.get("config") or {}).get("workload"), "forward_launch": (j.get("config") or {}).get("forward_launch"),
                          "roofline": {k: roof.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "avg_kernel_ms", "source")},
                          "overlap": (j.get("config") or {}).get("overlap"),
-                         "command": " ".join(f"{k}={v}" for k, v in (env_extra or {}).items()) + (" " if env_extra else "") + "python bench.py " + " ".join(extra),
+                         "command": " ".join(f"{k}={v}" for k, v in (env_extra or {}).items()) + (" " if env_extra else "") + "python bench.py --full " + " ".join(extra),
                          "seconds": time.perf_counter() - t0}
         except subprocess.TimeoutExpired:
-            out[name] = {"error": f"timed out after {limit} s", "seconds": time.perf_counter() - t0}
+            out[name] = {"error": f"timed out after {limit:.0f} s", "seconds": time.perf_counter() - t0}
+            stop = f"leg {name} timed out"
         except Exception as e:                                # a leg must never take the line down
             out[name] = {"error": repr(e)[:300], "seconds": time.perf_counter() - t0}
+            stop = f"leg {name} failed"
     return out
 
 

@@ -3,7 +3,7 @@
 
     python tools/step_anatomy.py [profiles/round5_kernel_stats.csv] [--forwards 19]
 
-`--forwards` = network forwards inside the profiled command (`bench.py --steps 10 --warmup 2` runs 19: seed probing, priming,
+`--forwards` = network forwards inside the profiled command (`bench.py --full --steps 10 --warmup 2` runs 19: seed probing, priming,
 warm-up, the timed steps and the per-kernel timing passes); it only scales the per-forward column."""
 import csv
 import sys
