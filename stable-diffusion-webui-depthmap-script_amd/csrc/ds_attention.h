@@ -20,6 +20,7 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 template <int BF16> struct at_traits;
 template <> struct at_traits<0> {
     typedef _Float16 T; typedef f16x8 V8;
+    static constexpr float max_finite = 65504.0f;
     static __device__ __forceinline__ f32x16 mfma(V8 a, V8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ T from_f32(float x) { return (_Float16)x; }
     static __device__ __forceinline__ float to_f32(T x) { return (float)x; }
@@ -32,6 +33,7 @@ template <> struct at_traits<0> {
 };
 template <> struct at_traits<1> {
     typedef __bf16 T; typedef bf16x8 V8;
+    static constexpr float max_finite = 3.38953139e38f;
     static __device__ __forceinline__ f32x16 mfma(V8 a, V8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ T from_f32(float x) { return (__bf16)x; }
     static __device__ __forceinline__ float to_f32(T x) { return (float)x; }

@@ -952,7 +952,10 @@ __global__ __launch_bounds__(AT_THREADS, 2) void k_attention_fwd3(AttnParams P)
 }
 #endif
 
-// bias operand of version 2: [H][Np/32][Np/64][4 chunks][64 lanes][8], values bias / scale (scale = 1/8: exact)
+// bias operand of version 2: [H][Np/32][Np/64][4 chunks][64 lanes][8], values bias / scale (scale = 1/8: exact), saturated at the
+// operand type's largest finite value: the bias MFMAs multiply this operand by an identity matrix, and an infinite entry times its
+// zeros would turn the whole row NaN.  In float16 that is |bias| <= 8188 natural units -- a -1e4 "mask" entry stays a key with weight
+// exp(-8188) = 0.
 template <int BF16>
 __global__ void k_attention_bias_pack2(const float *__restrict__ bias, typename at_traits<BF16>::T *__restrict__ out,
                                        int H, int n, int Np, float mul)
@@ -967,7 +970,7 @@ __global__ void k_attention_bias_pack2(const float *__restrict__ bias, typename 
         const int q = qb * 32 + 16 * (c & 1) + 8 * (lane >> 5) + t;
         const int k = kt * AT_KB + 32 * (c >> 1) + (lane & 31);
         const float v = (q < n && k < n) ? bias[((size_t)h * n + q) * n + k] * mul : 0.f;
-        out[idx] = TR::from_f32(v);
+        out[idx] = TR::from_f32(fminf(fmaxf(v, -TR::max_finite), TR::max_finite));
     }
 }
 

@@ -1084,13 +1084,72 @@ DS_API int ds_bias_act_nhwc(ds_ctx *ctx, const void *x, const void *bias, const 
 // 52 GroupNorms per image, and at batch 1 -- BASELINE config 2, a latency line -- torch spends three launches on each: RowwiseMoments
 // (one workgroup per group = 32 workgroups on 256 CUs: 15.5 us), ComputeFusedParams, the element-wise kernel, then a separate ReLU
 // and, behind norm3, a separate add + ReLU: 1.3 ms of a 4.8 ms image.  Here: one launch for the moments -- every (image, group) split
-// over up to 32 workgroups, float32 sum / sum of squares per slice -- and one that combines the slices in float64 (mean, var =
-// E[x^2] - mean^2 with the population variance, rstd = 1 / sqrt(var + eps) as torch), and applies y = x * (rstd gamma_c) + (beta_c -
-// mean rstd gamma_c) [+ res] [relu] in float32, rounded once to the activation's type.
+// over up to 32 workgroups -- and one that combines the slices and applies y = (x - mean) * (rstd gamma_c) + beta_c [+ res] [relu]
+// in float32, rounded once to the activation's type (population variance, rstd = 1 / sqrt(var + eps) as torch).  Centring x before
+// the scale keeps a constant group at beta exactly; torch's x * a + (beta - mean a) loses |mean a| 2^-24 to the cancellation.
+// The moments are float64 sums of x - P and (x - P)^2 around the group's first value P, which every slice reads: float32 sums around
+// a value of their own -- a wave's first value in k_gn_fused (at most 5120 values), each vector's first in k_gn_moments -- so no common
+// mode is left to cancel, shifted to P in float64; waves and slices add float64 sums.  Then mean = P + S / N and M2 = Q - S^2 / N, whose
+// cancellation is bounded by (mean - P)^2 / var <= N because P is one of the values.  A group whose mean is 1000 standard deviations
+// away from zero keeps its variance to ~1e-13; the E[x^2] - mean^2 form over float32 sums did not (relative error ~1e-7 (mean / std)^2).
 #define GN_MAX_SPLIT 32
 #define GN_MAX_NG 4096           // (images x groups) of one call: the moments block is allocated once at this size -- captured graphs hold its address
+
+typedef float gn_f2 __attribute__((ext_vector_type(2)));
+
+// float32 sums of x - v0 and (x - v0)^2 over one vector of 8 values, in two lanes of packed math
+template <typename T>
+__device__ __forceinline__ void gn_sum8(const T (&xv)[8], float v0, gn_f2 &s2, gn_f2 &q2)
+{
+    const gn_f2 p2 = {v0, v0};
+#pragma unroll
+    for (int t = 0; t < 8; t += 2) {
+        const gn_f2 d = gn_f2{(float)xv[t], (float)xv[t + 1]} - p2;
+        s2 += d;
+        q2 = __builtin_elementwise_fma(d, d, q2);
+    }
+}
+
+// float32 sums of n values around v0, shifted to the group's pivot P in float64 and added to the sums (S, Q) of x - P
+__device__ __forceinline__ void gn_shift_add(gn_f2 s2, gn_f2 q2, float v0, double n, double pv, double &S, double &Q)
+{
+    const double t0 = (double)v0 - pv, ds = (double)s2.x + (double)s2.y;
+    S += ds + n * t0;
+    Q += ((double)q2.x + (double)q2.y) + t0 * (2.0 * ds + n * t0);
+}
+
+// y = (x - mean) * a + b [+ res] [relu] for one vector, packed
+template <typename T>
+__device__ __forceinline__ void gn_apply8(const T (&xv)[8], const T (&rv)[8], bool res, int relu, float mean, float a, float b, T (&ov)[8])
+{
+    const gn_f2 m2 = {mean, mean}, a2 = {a, a}, b2 = {b, b};
+#pragma unroll
+    for (int t = 0; t < 8; t += 2) {
+        gn_f2 f = __builtin_elementwise_fma(gn_f2{(float)xv[t], (float)xv[t + 1]} - m2, a2, b2);
+        if (res) f += gn_f2{(float)rv[t], (float)rv[t + 1]};
+        if (relu) { f.x = f.x < 0.f ? 0.f : f.x; f.y = f.y < 0.f ? 0.f : f.y; }
+        ov[t] = (T)f.x; ov[t + 1] = (T)f.y;
+    }
+}
+
+__device__ __forceinline__ void gn_wave_sum(double &s, double &q)
+{
+#pragma unroll
+    for (int sft = 32; sft > 0; sft >>= 1) { s += __shfl_xor(s, sft, 64); q += __shfl_xor(q, sft, 64); }
+}
+
+// mean and rstd of a group of n values from the float64 sums of x - P
+__device__ __forceinline__ void gn_stats(double s, double q, double pv, int n, float eps, float *out)
+{
+    const double m = s / (double)n;
+    double var = (q - s * m) / (double)n;
+    if (var < 0.0) var = 0.0;
+    out[0] = (float)(pv + m);
+    out[1] = (float)(1.0 / sqrt(var + (double)eps));
+}
+
 template <int BF16>
-__global__ __launch_bounds__(256) void k_gn_moments(const void *x_, float2 *partial, int group_len, int splits)
+__global__ __launch_bounds__(256) void k_gn_moments(const void *x_, double2 *partial, int group_len, int splits)
 {
     typedef typename eo_traits<BF16>::T T;
     const int sp = blockIdx.x, ng = blockIdx.y;              // slice of the group, (image * groups + group)
@@ -1098,44 +1157,38 @@ __global__ __launch_bounds__(256) void k_gn_moments(const void *x_, float2 *part
     const int vecs = group_len >> 3;
     const int per = (vecs + splits - 1) / splits;
     const int v0 = sp * per, v1 = min(vecs, v0 + per);
-    float s = 0.f, q = 0.f;
+    const double pv = (double)(float)x[0];
+    double s = 0.0, q = 0.0;
     for (int v = v0 + threadIdx.x; v < v1; v += 256) {
         T xv[8];
         __builtin_memcpy(xv, x + (size_t)v * 8, 16);
-#pragma unroll
-        for (int t = 0; t < 8; t++) { const float f = (float)xv[t]; s += f; q = __builtin_fmaf(f, f, q); }
+        gn_f2 s2 = {0.f, 0.f}, q2 = {0.f, 0.f};
+        gn_sum8(xv, (float)xv[0], s2, q2);                  // a thread may hold many vectors here: float32 spans one of them
+        gn_shift_add(s2, q2, (float)xv[0], 8.0, pv, s, q);
     }
-#pragma unroll
-    for (int sft = 32; sft > 0; sft >>= 1) { s += __shfl_xor(s, sft, 64); q += __shfl_xor(q, sft, 64); }
-    __shared__ float2 red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = make_float2(s, q);
+    gn_wave_sum(s, q);
+    __shared__ double2 red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = make_double2(s, q);
     __syncthreads();
     if (threadIdx.x == 0) {
-        float2 r = red[0];
+        double2 r = red[0];
         for (int k = 1; k < 4; k++) { r.x += red[k].x; r.y += red[k].y; }
         partial[(size_t)ng * GN_MAX_SPLIT + sp] = r;
     }
 }
 
 template <int BF16>
-__global__ __launch_bounds__(256) void k_gn_apply(const void *x_, const float2 *partial, const void *gamma_, const void *beta_, const void *res_,
+__global__ __launch_bounds__(256) void k_gn_apply(const void *x_, const double2 *partial, const void *gamma_, const void *beta_, const void *res_,
                                                   void *out_, int group_len, int splits, int hw, int cpg, int groups, float eps, int relu, int chunks)
 {
     typedef typename eo_traits<BF16>::T T;
     const int ck = blockIdx.x, ng = blockIdx.y, g = ng % groups;
     __shared__ float s_stat[2];
     if (threadIdx.x < 64) {
-        double s = 0.0, q = 0.0;
-        if ((int)threadIdx.x < splits) { const float2 p = partial[(size_t)ng * GN_MAX_SPLIT + threadIdx.x]; s = p.x; q = p.y; }
-#pragma unroll
-        for (int sft = 32; sft > 0; sft >>= 1) { s += __shfl_xor(s, sft, 64); q += __shfl_xor(q, sft, 64); }
-        if (threadIdx.x == 0) {
-            const double mean = s / (double)group_len;
-            double var = q / (double)group_len - mean * mean;
-            if (var < 0.0) var = 0.0;
-            s_stat[0] = (float)mean;
-            s_stat[1] = (float)(1.0 / sqrt(var + (double)eps));
-        }
+        double s = 0.0, q = 0.0;                               // an empty slice (none with splits <= group_len / 4096) adds nothing
+        if ((int)threadIdx.x < splits) { const double2 p = partial[(size_t)ng * GN_MAX_SPLIT + threadIdx.x]; s = p.x; q = p.y; }
+        gn_wave_sum(s, q);
+        if (threadIdx.x == 0) gn_stats(s, q, (double)(float)((const T *)x_ + (size_t)ng * group_len)[0], group_len, eps, s_stat);
     }
     __syncthreads();
     const float mean = s_stat[0], rstd = s_stat[1];
@@ -1147,24 +1200,18 @@ __global__ __launch_bounds__(256) void k_gn_apply(const void *x_, const float2 *
     const int v0 = ck * per, v1 = min(vecs, v0 + per);
     for (int v = v0 + threadIdx.x; v < v1; v += 256) {
         const int c = g * cpg + (v * 8) / hw;                // hw % 8 == 0: the 8 values belong to one channel
-        const float a = rstd * (float)gamma[c], b = (float)beta[c] - mean * a;
+        const float a = rstd * (float)gamma[c], b = (float)beta[c];
         T xv[8], rv[8], ov[8];
         __builtin_memcpy(xv, x + (size_t)v * 8, 16);
         if (res) __builtin_memcpy(rv, res + (size_t)v * 8, 16);
-#pragma unroll
-        for (int t = 0; t < 8; t++) {
-            float f = __builtin_fmaf((float)xv[t], a, b);
-            if (res) f += (float)rv[t];
-            if (relu) f = f < 0.f ? 0.f : f;
-            ov[t] = (T)f;
-        }
+        gn_apply8(xv, rv, res != nullptr, relu, mean, a, b, ov);
         __builtin_memcpy(out + (size_t)v * 8, ov, 16);
     }
 }
 
 // One launch when a group fits the registers of one workgroup (1024 threads x up to 10 vectors of 8 values = 81.9 k values: every
 // GroupNorm of the ResNetV2 stem at 384 x 384 -- at most 73.7 k): the values are read ONCE, kept packed while the workgroup reduces the
-// moments, and written once.  Same arithmetic as the two-launch pair (float32 partial sums per thread and per wave, float64 combine).
+// moments, and written once.
 #define GN_FUSED_THREADS 1024
 #define GN_FUSED_VECS 10
 template <int BF16>
@@ -1178,36 +1225,45 @@ __global__ __launch_bounds__(GN_FUSED_THREADS) void k_gn_fused(const void *x_, c
     T *out = (T *)out_ + (size_t)ng * group_len;
     const int vecs = group_len >> 3;
     uint4 keep[GN_FUSED_VECS];
-    float s = 0.f, q = 0.f;
+    // all loads in flight at once: a lane past the group re-reads the group's last vector (a guard around the loads made the compiler
+    // wait for each one before issuing the next)
+#pragma unroll
+    for (int k = 0; k < GN_FUSED_VECS; k++) keep[k] = *(const uint4 *)(x + (size_t)min(tid + k * GN_FUSED_THREADS, vecs - 1) * 8);
+    const double pv = (double)(float)x[0];
+    // float32 sums around the wave's first value (its lane 0 holds the wave's lowest vector) over the wave's <= 5120 values, reduced
+    // across the wave in float32, then shifted to P once per wave
+    float v0 = 0.f;
+    if (tid < vecs) { T x0[8]; __builtin_memcpy(x0, &keep[0], 16); v0 = (float)x0[0]; }
+    v0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v0)));
+    gn_f2 s2 = {0.f, 0.f}, q2 = {0.f, 0.f};
+    int cnt = 0;
 #pragma unroll
     for (int k = 0; k < GN_FUSED_VECS; k++) {
         const int v = tid + k * GN_FUSED_THREADS;
         if (v < vecs) {
-            keep[k] = *(const uint4 *)(x + (size_t)v * 8);
             T xv[8];
             __builtin_memcpy(xv, &keep[k], 16);
-#pragma unroll
-            for (int t = 0; t < 8; t++) { const float f = (float)xv[t]; s += f; q = __builtin_fmaf(f, f, q); }
+            gn_sum8(xv, v0, s2, q2);
+            cnt += 8;
         }
     }
 #pragma unroll
-    for (int sft = 32; sft > 0; sft >>= 1) { s += __shfl_xor(s, sft, 64); q += __shfl_xor(q, sft, 64); }
-    __shared__ float2 red[GN_FUSED_THREADS / 64];
+    for (int sft = 32; sft > 0; sft >>= 1) {
+        s2.x += __shfl_xor(s2.x, sft, 64); s2.y += __shfl_xor(s2.y, sft, 64);
+        q2.x += __shfl_xor(q2.x, sft, 64); q2.y += __shfl_xor(q2.y, sft, 64);
+        cnt += __shfl_xor(cnt, sft, 64);
+    }
+    double s = 0.0, q = 0.0;
+    gn_shift_add(s2, q2, v0, (double)cnt, pv, s, q);
+    __shared__ double2 red[GN_FUSED_THREADS / 64];
     __shared__ float s_stat[2];
-    if ((tid & 63) == 0) red[tid >> 6] = make_float2(s, q);
+    if ((tid & 63) == 0) red[tid >> 6] = make_double2(s, q);
     __syncthreads();
     if (tid < 64) {
-        double ds = 0.0, dq = 0.0;
-        if (tid < GN_FUSED_THREADS / 64) { ds = red[tid].x; dq = red[tid].y; }
-#pragma unroll
-        for (int sft = 32; sft > 0; sft >>= 1) { ds += __shfl_xor(ds, sft, 64); dq += __shfl_xor(dq, sft, 64); }
-        if (tid == 0) {
-            const double mean = ds / (double)group_len;
-            double var = dq / (double)group_len - mean * mean;
-            if (var < 0.0) var = 0.0;
-            s_stat[0] = (float)mean;
-            s_stat[1] = (float)(1.0 / sqrt(var + (double)eps));
-        }
+        double ws = 0.0, wq = 0.0;
+        if (tid < GN_FUSED_THREADS / 64) { ws = red[tid].x; wq = red[tid].y; }
+        gn_wave_sum(ws, wq);
+        if (tid == 0) gn_stats(ws, wq, pv, group_len, eps, s_stat);
     }
     __syncthreads();
     const float mean = s_stat[0], rstd = s_stat[1];
@@ -1216,17 +1272,11 @@ __global__ __launch_bounds__(GN_FUSED_THREADS) void k_gn_fused(const void *x_, c
         const int v = tid + k * GN_FUSED_THREADS;
         if (v < vecs) {
             const int c = g * cpg + (v * 8) / hw;
-            const float a = rstd * (float)gamma[c], b = (float)beta[c] - mean * a;
+            const float a = rstd * (float)gamma[c], b = (float)beta[c];
             T xv[8], rv[8], ov[8];
             __builtin_memcpy(xv, &keep[k], 16);
             if (res) __builtin_memcpy(rv, res + (size_t)v * 8, 16);
-#pragma unroll
-            for (int t = 0; t < 8; t++) {
-                float f = __builtin_fmaf((float)xv[t], a, b);
-                if (res) f += (float)rv[t];
-                if (relu) f = f < 0.f ? 0.f : f;
-                ov[t] = (T)f;
-            }
+            gn_apply8(xv, rv, res != nullptr, relu, mean, a, b, ov);
             __builtin_memcpy(out + (size_t)v * 8, ov, 16);
         }
     }
@@ -1248,10 +1298,10 @@ DS_API int ds_group_norm_nchw(ds_ctx *ctx, const void *x, const void *gamma, con
     const int group_len = (int)group_len_ll;
     int splits = group_len / 4096; if (splits < 1) splits = 1; if (splits > GN_MAX_SPLIT) splits = GN_MAX_SPLIT;
     int chunks = group_len / 8192; if (chunks < 1) chunks = 1; if (chunks > 64) chunks = 64;
-    const int rc = ds_ctx_reserve(ctx, &ctx->gn_ws, &ctx->gn_ws_bytes, (size_t)GN_MAX_NG * GN_MAX_SPLIT * sizeof(float2));
+    const int rc = ds_ctx_reserve(ctx, &ctx->gn_ws, &ctx->gn_ws_bytes, (size_t)GN_MAX_NG * GN_MAX_SPLIT * sizeof(double2));
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    float2 *partial = (float2 *)ctx->gn_ws;
+    double2 *partial = (double2 *)ctx->gn_ws;
     // few groups of a size one workgroup holds in registers (the batch-1 stem): ONE launch; many or larger groups: moments + apply,
     // every group spread over several workgroups.  DS_GN_FUSED=0: always the pair (A/B runs)
     static const int s_fused = getenv("DS_GN_FUSED") ? atoi(getenv("DS_GN_FUSED")) : 1;
