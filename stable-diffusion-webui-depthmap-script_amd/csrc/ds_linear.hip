@@ -23,15 +23,15 @@
 //     fragment read (16-byte slot ^= (row >> 1) & 7 inside a 128-byte row: every 16-lane group of a ds_read_b128 then
 //     covers all 16 slots of the 256-byte bank row; the XOR stays inside one 128-byte line, so global coalescing is intact).
 //   * the K loop is 8 phases per two K-tiles.  Each phase = {fragment reads of ONE half-tile, DMA issue of ONE
-//     half-tile, counted vmcnt} barrier {8 MFMA 32x32x16 on one quadrant} barrier.  The two wave-rows run staggered
+//     half-tile, counted vmcnt} barrier {16 MFMA 16x16x32 on one quadrant (the convolutions: 8 MFMA 32x32x16)} barrier.  The two wave-rows run staggered
 //     by one barrier, so at any time one wave of a SIMD is in its MFMA part while the other one is in its memory part.
 //     A half-tile is staged 6 phases before it is read; `s_waitcnt vmcnt(10)` (5 half-tiles stay in flight) never
 //     drains the queue.  Hazards (both directions) are argued next to the schedule table below and checked by
 //     tools/linear_model.py (tests/test_linear_model.py).
 //   * operands go into the MFMA swapped (W fragment as "A", x fragment as "B"), so an accumulator register holds 4
 //     consecutive output COLUMNS of one row: the epilogue adds the bias / residuals and applies the activation in fp32 on
-//     the accumulator (not on a rounded half); a half-wave exchange (v_permlane32_swap) widens that to 8 columns = one
-//     16-byte store per lane.
+//     the accumulator (not on a rounded half); an exchange between 16-lane rows (v_permlane16_swap; 32x32x16: the half-wave
+//     v_permlane32_swap) widens that to 8 columns = one 16-byte store per lane.
 //
 // Workgroup -> tile mapping is XCD-aware: the eight XCDs take contiguous ranges of the tile list, which is ordered so that
 // the 32 workgroups resident on one XCD work on 8 row panels x 4 column panels at a time.
@@ -46,6 +46,16 @@ typedef __bf16 lbf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 lf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 lbf16x4 __attribute__((ext_vector_type(4)));
 typedef float lf32x16 __attribute__((ext_vector_type(16)));
+typedef float lf32x4 __attribute__((ext_vector_type(4)));
+
+// MFMA shape of k_linear256's K loop: 1 = v_mfma_f32_16x16x32 (a 16 x 32 operand fragment per ds_read_b128), 0 = the
+// 32x32x16 generation it replaced (32 x 16 fragments).  Same tiles, LDS image, DMA schedule and counted waits; the fp32 chain
+// groups 32 products per MFMA instead of 16.
+#if defined(DS_EXPERIMENTS) && defined(DS_LIN_MFMA32)
+#define LN_MF16 0
+#else
+#define LN_MF16 1
+#endif
 
 #define LN_THREADS 512
 #define LN_LDS_BYTES 131072
@@ -56,6 +66,7 @@ template <int BF16> struct ln_traits;
 template <> struct ln_traits<0> {
     typedef _Float16 T; typedef lf16x8 V8; typedef lf16x4 V4;
     static __device__ __forceinline__ lf32x16 mfma(V8 a, V8 b, lf32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ lf32x4 mfma16(V8 a, V8 b, lf32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
     // max(v, 0) on the 8 packed halves of a fragment: 4 v_pk_max_f16 (inline asm: the builtin puts a canonicalising v_pk_max in
     // front of every one of them)
     static __device__ __forceinline__ V8 relu(V8 v)
@@ -73,6 +84,7 @@ template <> struct ln_traits<0> {
 template <> struct ln_traits<1> {
     typedef __bf16 T; typedef lbf16x8 V8; typedef lbf16x4 V4;
     static __device__ __forceinline__ lf32x16 mfma(V8 a, V8 b, lf32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ lf32x4 mfma16(V8 a, V8 b, lf32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
     // max(v, 0) on 8 packed bfloat16 (no packed bfloat16 maximum on gfx950): clear every half whose sign bit is set
     static __device__ __forceinline__ V8 relu(V8 v)
     {
@@ -229,6 +241,7 @@ __device__ __forceinline__ void ln_dma_v(const void *ptr, unsigned lds_uniform)
 #define LN_STAGGER() 0
 #endif
 #define LN_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+template <int N> __device__ __forceinline__ void ln_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 #define LN_WAIT_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #define LN_BARRIER()                              \
     do {                                          \
@@ -341,43 +354,64 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
         }                                                                                                                \
     } while (0)
 
-    // ---- fragment reads: lane reads LDS row (lane & 31) of its 32-row block, slot 2*ks + (lane >> 5), swizzled -----------
-    unsigned offA[4], offB[4];
+    // ---- fragment reads.  16x16x32 (MF16): lane reads LDS row (lane & 15) of its 16-row block, slot 4*ks + (lane >> 4); a
+    // 16-lane group reads 16 consecutive rows at one logical slot, which the XOR spreads over all 16 slots of two bank rows.
+    // 32x32x16: lane reads LDS row (lane & 31) of its 32-row block, slot 2*ks + (lane >> 5).  Both swizzled by the row.
+    constexpr bool MF16 = LN_MF16 && CONV == 0;
+    constexpr int NKS = MF16 ? 2 : 4;                           // k steps per K-tile of 64
+    unsigned offA[NKS], offB[NKS];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        const unsigned sl = (unsigned)((2 * ks + (lane >> 5)) ^ ((lane >> 1) & 7)) << 4;
-        offA[ks] = (unsigned)(wr * 64 + (lane & 31)) * 128u + sl;
-        offB[ks] = LN_B_BASE + (unsigned)(wc * 32 + (lane & 31)) * 128u + sl;
+    for (int ks = 0; ks < NKS; ++ks) {
+        const int lrow = MF16 ? (lane & 15) : (lane & 31);
+        const unsigned sl = (unsigned)((MF16 ? 4 * ks + (lane >> 4) : 2 * ks + (lane >> 5)) ^ ((lane >> 1) & 7)) << 4;
+        offA[ks] = (unsigned)(wr * 64 + lrow) * 128u + sl;
+        offB[ks] = LN_B_BASE + (unsigned)(wc * 32 + lrow) * 128u + sl;
     }
+    // MF16: this lane's 8 output columns inside a 32-column W half after the epilogue's permlane16 swap (16-lane group g holds
+    // columns 16 (g & 1) + 8 (g >> 1) .. + 7); 32x32x16: columns 8 (lane >> 5) + 16 k, k = 0, 1
+    const int c8 = MF16 ? 16 * ((lane >> 4) & 1) + 8 * (lane >> 5) : 8 * (lane >> 5);
+    constexpr int NBK = MF16 ? 1 : 2;                           // bias pieces per W half
+    constexpr int NBIAS = 2 * NBK;
     V8 bv[2][2];         // epilogue: bias of this wave's columns, [W half][k]: 8 columns each, kept packed
-    // loaded BEFORE the last iteration of a tile (in flight under its MFMAs).  Always exactly 4 loads -- a null bias reads 16
+    // loaded BEFORE the last iteration of a tile (in flight under its MFMAs).  Always exactly NBIAS loads -- a null bias reads 16
     // valid bytes of W instead and is zeroed afterwards -- because the last iteration's counted waits include them.  (The
     // LayerScale vector of EPI 3 is loaded in the epilogue next to the residuals: that variant waits there anyway.)
 #define LN_LOAD_BIAS()                                                                                                   \
     do {                                                                                                                 \
         const T *bias_ = (const T *)P.bias;                                                                              \
-        _Pragma("unroll") for (int hb_ = 0; hb_ < 2; ++hb_) _Pragma("unroll") for (int k_ = 0; k_ < 2; ++k_) {           \
-            const int c_ = bn0 + (NH ? wc * 32 : wc * 64 + hb_ * 32) + 8 * (lane >> 5) + 16 * k_;                        \
+        _Pragma("unroll") for (int hb_ = 0; hb_ < 2; ++hb_) _Pragma("unroll") for (int k_ = 0; k_ < NBK; ++k_) {         \
+            const int c_ = bn0 + (NH ? wc * 32 : wc * 64 + hb_ * 32) + c8 + 16 * k_;                                     \
             bv[hb_][k_] = *(const V8 *)(bias_ ? bias_ + c_ : (const T *)P.w);                                            \
         }                                                                                                                \
     } while (0)
 #define LN_ZERO_NULL_BIAS()                                                                                              \
     do {                                                                                                                 \
         if (!P.bias) {                                                                                                   \
-            _Pragma("unroll") for (int hb_ = 0; hb_ < 2; ++hb_) _Pragma("unroll") for (int k_ = 0; k_ < 2; ++k_)         \
+            _Pragma("unroll") for (int hb_ = 0; hb_ < 2; ++hb_) _Pragma("unroll") for (int k_ = 0; k_ < NBK; ++k_)       \
                 _Pragma("unroll") for (int t_ = 0; t_ < 8; ++t_) bv[hb_][k_][t_] = (T)0.f;                               \
         }                                                                                                                \
     } while (0)
-    V8 fa[2][2][4];      // [half][row block][k step]   x fragments
-    V8 fb[2][4];         // [half][k step]              W fragments
-    lf32x16 acc[2][2][2];  // [x half][row block][W half]
+    // (each instantiation uses one of the two register layouts; the other one is never touched and compiles away)
+    V8 fa[2][2][4];          // 32x32x16: [half][32-row block][k step]     x fragments
+    V8 fb[2][4];             //           [half][k step]                   W fragments
+    lf32x16 acc[2][2][2];    //           [x half][row block][W half]
+    V8 fa16[2][4][2];        // 16x16x32: [half][16-row block][k step]
+    V8 fb16[2][2][2];        //           [half][16-column block][k step]
+    lf32x4 acc16[2][4][2][2];//           [x half][row block][W half][column block]
 
 #define LN_READ_A(h, s)                                                                                                  \
-    _Pragma("unroll") for (int rb_ = 0; rb_ < 2; ++rb_) _Pragma("unroll") for (int ks_ = 0; ks_ < 4; ++ks_)              \
-        fa[h][rb_][ks_] = *(const V8 *)(lds + offA[ks_] + ((h) * 2 * LN_HALF + (s) * LN_HALF + rb_ * 4096))
+    do {                                                                                                                 \
+        if constexpr (MF16) {                                                                                            \
+            _Pragma("unroll") for (int rb_ = 0; rb_ < 4; ++rb_) _Pragma("unroll") for (int ks_ = 0; ks_ < 2; ++ks_)      \
+                fa16[h][rb_][ks_] = *(const V8 *)(lds + offA[ks_] + ((h) * 2 * LN_HALF + (s) * LN_HALF + rb_ * 2048));   \
+        } else {                                                                                                         \
+            _Pragma("unroll") for (int rb_ = 0; rb_ < 2; ++rb_) _Pragma("unroll") for (int ks_ = 0; ks_ < 4; ++ks_)      \
+                fa[h][rb_][ks_] = *(const V8 *)(lds + offA[ks_] + ((h) * 2 * LN_HALF + (s) * LN_HALF + rb_ * 4096));     \
+        }                                                                                                                \
+    } while (0)
     // CONV 2: ReLU on the x operand (the `conv1(relu(x))` of a residual unit, dmidas/blocks.py:361-363): applied to the fragments
     // in the MEMORY part of the phase that read them -- 32 packed maxima per wave, issued as the reads return, beside the other
-    // wave-row's MFMAs -- instead of a pass over the activation in front of the launch
+    // wave-row's MFMAs -- instead of a pass over the activation in front of the launch (the convolutions run the 32x32x16 form)
 #define LN_RELU_A(h)                                                                                                     \
     do {                                                                                                                 \
         if constexpr (CONV == 2) {                                                                                       \
@@ -386,13 +420,29 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
         }                                                                                                                \
     } while (0)
 #define LN_READ_B(h, s)                                                                                                  \
-    _Pragma("unroll") for (int ks_ = 0; ks_ < 4; ++ks_)                                                                  \
-        if (!(NH && (h) == 1)) fb[h][ks_] = *(const V8 *)(lds + offB[ks_] + ((h) * 2 * LN_HALF + (s) * LN_HALF))
-#define LN_MMA_PART(ha, hb, k0, k1)                                                                                      \
     do {                                                                                                                 \
-        if (!(NH && (hb) == 1))                                                                                          \
-        _Pragma("unroll") for (int ks_ = (k0); ks_ < (k1); ++ks_) _Pragma("unroll") for (int rb_ = 0; rb_ < 2; ++rb_)    \
-            acc[ha][rb_][hb] = TR::mfma(fb[hb][ks_], fa[ha][rb_][ks_], acc[ha][rb_][hb]);                                \
+        if constexpr (MF16) {                                                                                            \
+            _Pragma("unroll") for (int cb_ = 0; cb_ < 2; ++cb_) _Pragma("unroll") for (int ks_ = 0; ks_ < 2; ++ks_)      \
+                if (!(NH && (h) == 1)) fb16[h][cb_][ks_] = *(const V8 *)(lds + offB[ks_] + ((h) * 2 * LN_HALF + (s) * LN_HALF + cb_ * 2048)); \
+        } else {                                                                                                         \
+            _Pragma("unroll") for (int ks_ = 0; ks_ < 4; ++ks_)                                                          \
+                if (!(NH && (h) == 1)) fb[h][ks_] = *(const V8 *)(lds + offB[ks_] + ((h) * 2 * LN_HALF + (s) * LN_HALF)); \
+        }                                                                                                                \
+    } while (0)
+    // one quadrant: 16 x 16x16x32 (k step outermost: 8 independent accumulators between two dependent issues) or 8 x 32x32x16,
+    // 256 MFMA cycles either way
+#define LN_MMA_PART(ha, hb)                                                                                              \
+    do {                                                                                                                 \
+        if (!(NH && (hb) == 1)) {                                                                                        \
+            if constexpr (MF16) {                                                                                        \
+                _Pragma("unroll") for (int ks_ = 0; ks_ < 2; ++ks_) _Pragma("unroll") for (int rb_ = 0; rb_ < 4; ++rb_)  \
+                    _Pragma("unroll") for (int cb_ = 0; cb_ < 2; ++cb_)                                                  \
+                        acc16[ha][rb_][hb][cb_] = TR::mfma16(fb16[hb][cb_][ks_], fa16[ha][rb_][ks_], acc16[ha][rb_][hb][cb_]); \
+            } else {                                                                                                     \
+                _Pragma("unroll") for (int ks_ = 0; ks_ < 4; ++ks_) _Pragma("unroll") for (int rb_ = 0; rb_ < 2; ++rb_)  \
+                    acc[ha][rb_][hb] = TR::mfma(fb[hb][ks_], fa[ha][rb_][ks_], acc[ha][rb_][hb]);                        \
+            }                                                                                                            \
+        }                                                                                                                \
     } while (0)
 
     // ---- schedule ------------------------------------------------------------------------------------------------------
@@ -434,7 +484,7 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
     do {                                                                                                                 \
         LN_BARRIER(); LN_WAIT_LGKM0();                                                                                   \
         __builtin_amdgcn_s_setprio(1);                                                                                   \
-        LN_MMA_PART(ha, hb, 0, 4);                                                                                       \
+        LN_MMA_PART(ha, hb);                                                                                             \
         __builtin_amdgcn_s_setprio(0);                                                                                   \
         LN_BARRIER();                                                                                                    \
     } while (0)
@@ -453,28 +503,28 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
         constexpr int KIND = decltype(kind_c)::value;
         constexpr bool LAST = KIND == 1;
         const int e2 = 2 * i + 2, o2 = 2 * i + 3;
-        // (KIND 1: the 4 bias loads issued just before this iteration are YOUNGER than every DMA its phases
+        // (KIND 1: the NBIAS bias loads issued just before this iteration are YOUNGER than every DMA its phases
         // 0..4 wait for, so they add to the count; phase 5 waits for everything)
 #define LN_WAIT_HEAD()                                                                                                   \
         do {                                                                                                             \
             if constexpr (KIND == 2) { if constexpr (NH) LN_WAIT_VM(18); else LN_WAIT_VM(26); }                          \
-            else if constexpr (KIND == 1) LN_WAIT_VM(14);                                                                \
+            else if constexpr (KIND == 1) ln_wait_vm<10 + NBIAS>();                                                   \
             else LN_WAIT_VM(10);                                                                                         \
         } while (0)
         // phase 0
         LN_MEM(LN_READ_B(0, 0), LN_STAGE(1, 2 * i + 1, 1)); LN_WAIT_HEAD();
         LN_PHASE_END(0, 0);
         // phase 1
-        if constexpr (!LAST) { LN_MEM(LN_READ_B(1, 0), LN_STAGE(0, e2, 0)); LN_WAIT_HEAD(); } else { LN_READ_B(1, 0); LN_WAIT_VM(12); }
+        if constexpr (!LAST) { LN_MEM(LN_READ_B(1, 0), LN_STAGE(0, e2, 0)); LN_WAIT_HEAD(); } else { LN_READ_B(1, 0); ln_wait_vm<8 + NBIAS>(); }
         LN_PHASE_END(0, 1);
         // phase 2
-        if constexpr (!LAST) { LN_MEM(LN_READ_A(1, 0), LN_STAGE(2, e2, 0)); LN_RELU_A(1); LN_WAIT_HEAD(); } else { LN_READ_A(1, 0); LN_RELU_A(1); LN_WAIT_VM(10); }
+        if constexpr (!LAST) { LN_MEM(LN_READ_A(1, 0), LN_STAGE(2, e2, 0)); LN_RELU_A(1); LN_WAIT_HEAD(); } else { LN_READ_A(1, 0); LN_RELU_A(1); ln_wait_vm<6 + NBIAS>(); }
         LN_PHASE_END(1, 1);
         // phase 3
-        if constexpr (!LAST) { LN_MEM(LN_READ_A(0, 1), LN_STAGE(3, e2, 0)); LN_RELU_A(0); LN_WAIT_HEAD(); } else { LN_READ_A(0, 1); LN_RELU_A(0); LN_WAIT_VM(8); }
+        if constexpr (!LAST) { LN_MEM(LN_READ_A(0, 1), LN_STAGE(3, e2, 0)); LN_RELU_A(0); LN_WAIT_HEAD(); } else { LN_READ_A(0, 1); LN_RELU_A(0); ln_wait_vm<4 + NBIAS>(); }
         LN_PHASE_END(1, 0);
         // phase 4
-        if constexpr (!LAST) { LN_MEM(LN_READ_B(0, 1), LN_STAGE(1, e2, 0)); LN_WAIT_HEAD(); } else { LN_READ_B(0, 1); LN_WAIT_VM(6); }
+        if constexpr (!LAST) { LN_MEM(LN_READ_B(0, 1), LN_STAGE(1, e2, 0)); LN_WAIT_HEAD(); } else { LN_READ_B(0, 1); ln_wait_vm<2 + NBIAS>(); }
         LN_PHASE_END(0, 0);
 #undef LN_WAIT_HEAD
         // phase 5
@@ -504,14 +554,27 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
     set_tile(blockIdx.x);
     LN_PROLOGUE();
     for (int orig = blockIdx.x;;) {
+    if constexpr (MF16) {
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
+        for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b)
+            for (int b = 0; b < 4; ++b)
 #pragma unroll
-            for (int c = 0; c < 2; ++c)
+                for (int c = 0; c < 2; ++c)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[a][b][c][r] = 0.f;
+                    for (int d = 0; d < 2; ++d)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) acc16[a][b][c][d][r] = 0.f;
+    } else {
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int c = 0; c < 2; ++c)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[a][b][c][r] = 0.f;
+    }
     // Late mode: in the queue ahead of the prologue's 14 loads is nothing (first tile) or the previous tile's epilogue stores,
     // which retire first (the counter is in order): "all but the last 10" covers A0 and B0 of K-tile 0 either way.
     // Early mode: [14 DMAs, 16 stores]: A0 and B0 of K-tile 0 are the 4 oldest of 30; the first tile of a workgroup has no
@@ -549,76 +612,66 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
 #pragma unroll
         for (int hb = 0; hb < 2; ++hb)
 #pragma unroll
-            for (int k = 0; k < 2; ++k) {
+            for (int k = 0; k < NBK; ++k) {
                 asm volatile("" ::"v"(bv[hb][k]));
             }
         set_tile(next);
         LN_PROLOGUE();
     }
 
-    // ---- epilogue ---------------------------------------------------------------------------------------------------------
-    // Register r of a 32 x 32 accumulator block = column (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of row lane & 31: a lane holds
-    // 4-column groups g = r >> 2, the other half-wave holds the groups in between.  One v_permlane32_swap per register pair
-    // (g = 2k, 2k+1) exchanges them so that lanes 0-31 end up with columns 16k .. 16k+7 and lanes 32-63 with 16k+8 .. 16k+15
-    // of their row, in fp32: bias, residuals (16-byte loads, all issued before the arithmetic) and the activation are applied
-    // on 8 consecutive columns and the result leaves as one 16-byte store per lane (32 bytes of a row per instruction).
-    // (Round 2 sent the plain GEMM's results through LDS to store full 128-byte lines: qk 160 -> 152 us.  In early mode that
-    // LDS already holds the next tile's operands, and the variant is gone.)
-    V8 gv[2][2];                                                // EPI 3: the per-column LayerScale factors, packed like the bias
-    if (EPI == 3) {
+    if constexpr (MF16) {
+        // ---- epilogue ---------------------------------------------------------------------------------------------------------
+        // Register r of a 16 x 16 accumulator block = column 4 (lane >> 4) + r of row lane & 15: the 16-lane group g holds column
+        // group g of both column blocks of a W half.  One v_permlane16_swap per register pair (column block 0, 1) exchanges the odd
+        // groups of block 0 with the even groups of block 1, so that group g ends up with the 8 consecutive columns c8 = 16 (g & 1)
+        // + 8 (g >> 1) .. + 7 of the 32-column half, in fp32: bias, residuals (16-byte loads, all issued before the arithmetic) and
+        // the activation are applied on them and the result leaves as one 16-byte store per lane -- one per (ha, rb, hb): 16 per
+        // tile, the count the early mode's waits rely on.
+        V8 gv[2];                                                   // EPI 3: the per-column LayerScale factors, packed like the bias
+        if (EPI == 3) {
 #pragma unroll
-        for (int hb = 0; hb < 2; ++hb)
+            for (int hb = 0; hb < 2; ++hb) gv[hb] = *(const V8 *)((const T *)P.gamma + cbn0 + (NH ? wc * 32 : wc * 64 + hb * 32) + c8);
+        }
+        constexpr int NHB = NH ? 1 : 2;                             // W halves with results (NH: the B0 half alone)
+        const int wcol = NH ? wc * 32 : wc * 64;
 #pragma unroll
-            for (int k = 0; k < 2; ++k) gv[hb][k] = *(const V8 *)((const T *)P.gamma + cbn0 + (NH ? wc * 32 : wc * 64 + hb * 32) + hi8 + 16 * k);
-    }
-    constexpr int NHB = NH ? 1 : 2;                             // W halves with results (NH: the B0 half alone)
-    const int wcol = NH ? wc * 32 : wc * 64;
+        for (int ha = 0; ha < 2; ++ha)
 #pragma unroll
-    for (int ha = 0; ha < 2; ++ha)
+            for (int rb = 0; rb < 4; ++rb) {
+                const int row = cbm0 + wr * 128 + ha * 64 + rb * 16 + (lane & 15);
+                const int col = cbn0 + wcol + c8;                   // + 32 hb
+                const size_t o0 = (size_t)row * P.ldy + col;
+                V8 ra[2], rb2[2];                                    // residual pieces [W half]
+                constexpr bool LNF = EPI == 4 || EPI == 5;
+                float2 st_row = {1.f, 0.f};                          // LNF, row-major output: {rstd, -mean rstd} of this lane's token
+                float cs_row = 0.f;                                  // LNF, VT: colsum of this lane's output channel
+                static_assert(!LNF || VT == 0 || VT == 1, "the folded LayerNorm exists for the row-major and the V^T store only");
+                if (LNF && VT == 0) st_row = P.ln_stats[row];
+                if (LNF && VT == 1) cs_row = P.ln_colsum[row];
 #pragma unroll
-        for (int rb = 0; rb < 2; ++rb) {
-            const int rl = ha * 64 + rb * 32 + (lane & 31);     // row inside the wave tile
-            const size_t o0 = (size_t)(cbm0 + wr * 128 + rl) * P.ldy + cbn0 + wcol + hi8;
-            // VT: where the 8 columns of piece (hb, k) go (per batch element [channels][tokens]); else o0 + hb * 32 + 16 * k
-            auto out_off = [&](const int hb_, const int k_) -> size_t {
-                return VT ? ln_out_off<VT>(P, cbm0 + wr * 128 + rl, cbn0 + wcol + hi8 + hb_ * 32 + 16 * k_) : o0 + hb_ * 32 + 16 * k_;
-            };
-            V8 ra[2][2], rb2[2][2];                              // residual pieces [W half][k]
-            constexpr bool LNF = EPI == 4 || EPI == 5;
-            float2 st_row = {1.f, 0.f};                          // LNF, row-major output: {rstd, -mean rstd} of this lane's token
-            float cs_row = 0.f;                                  // LNF, VT: colsum of this lane's output channel
-            static_assert(!LNF || VT == 0 || VT == 1, "the folded LayerNorm exists for the row-major and the V^T store only");
-            if (LNF && VT == 0) st_row = P.ln_stats[cbm0 + wr * 128 + rl];
-            if (LNF && VT == 1) cs_row = P.ln_colsum[cbm0 + wr * 128 + rl];
-#pragma unroll
-            for (int hb = 0; hb < NHB; ++hb)
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    if (RES >= 1) ra[hb][k] = *(const V8 *)(r1 + (VT == 3 ? ln_res_off<VT>(P, cbm0 + wr * 128 + rl, cbn0 + wcol + hi8 + hb * 32 + 16 * k) : o0 + hb * 32 + 16 * k));
-                    if (RES >= 2) rb2[hb][k] = *(const V8 *)(r2 + o0 + hb * 32 + 16 * k);
+                for (int hb = 0; hb < NHB; ++hb) {
+                    if (RES >= 1) ra[hb] = *(const V8 *)(r1 + (VT == 3 ? ln_res_off<VT>(P, row, col + hb * 32) : o0 + hb * 32));
+                    if (RES >= 2) rb2[hb] = *(const V8 *)(r2 + o0 + hb * 32);
                 }
 #pragma unroll
-            for (int hb = 0; hb < NHB; ++hb)
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
+                for (int hb = 0; hb < NHB; ++hb) {
                     float v[8];
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
-                        // (copies first: __builtin_bit_cast applied to a vector ELEMENT reads element 0 with this clang)
-                        const float fa = acc[ha][rb][hb][8 * k + t], fb = acc[ha][rb][hb][8 * k + 4 + t];
-                        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(fa), __float_as_uint(fb), false, false);
+                        const float fa = acc16[ha][rb][hb][0][t], fb = acc16[ha][rb][hb][1][t];
+                        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(fa), __float_as_uint(fb), false, false);
                         v[t] = __uint_as_float(sw[0]);
                         v[4 + t] = __uint_as_float(sw[1]);
                     }
                     V8 o;
-                    if (LNF) {                                   // fold the LayerNorm back in (fp32, before bias and activation)
-                        const int c0 = cbn0 + wcol + hi8 + hb * 32 + 16 * k;
+                    if (LNF) {                                       // fold the LayerNorm back in (fp32, before bias and activation)
+                        const int c0 = col + hb * 32;
                         if (!VT) {
                             const float4 s0 = *(const float4 *)(P.ln_colsum + c0), s1 = *(const float4 *)(P.ln_colsum + c0 + 4);
                             const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
 #pragma unroll
                             for (int t = 0; t < 8; ++t) v[t] = __builtin_fmaf(v[t], st_row.x, st_row.y * sc[t]);
-                        } else {                                 // VT: the 8 columns are 8 tokens, the row is one channel
+                        } else {                                     // VT: the 8 columns are 8 tokens, the row is one channel
                             const float4 *sp = (const float4 *)(P.ln_stats + c0);
                             const float4 q0 = sp[0], q1 = sp[1], q2 = sp[2], q3 = sp[3];
                             const float rs[8] = {q0.x, q0.z, q1.x, q1.z, q2.x, q2.z, q3.x, q3.z};
@@ -629,19 +682,108 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
                     }
 #pragma unroll
                     for (int t = 0; t < 8; t += 2) {
-                        lf32x2 u = {v[t] + (float)bv[hb][k][t], v[t + 1] + (float)bv[hb][k][t + 1]};
-                        if (EPI == 3) u *= (lf32x2){(float)gv[hb][k][t], (float)gv[hb][k][t + 1]};
-                        if (RES >= 1) u += (lf32x2){(float)ra[hb][k][t], (float)ra[hb][k][t + 1]};
-                        if (RES >= 2) u += (lf32x2){(float)rb2[hb][k][t], (float)rb2[hb][k][t + 1]};
+                        lf32x2 u = {v[t] + (float)bv[hb][0][t], v[t + 1] + (float)bv[hb][0][t + 1]};
+                        if (EPI == 3) u *= (lf32x2){(float)gv[hb][t], (float)gv[hb][t + 1]};
+                        if (RES >= 1) u += (lf32x2){(float)ra[hb][t], (float)ra[hb][t + 1]};
+                        if (RES >= 2) u += (lf32x2){(float)rb2[hb][t], (float)rb2[hb][t + 1]};
                         if (EPI == 1 || EPI == 5) u = ln_gelu2(u);
                         if (EPI == 2) u = (lf32x2){fmaxf(u[0], 0.f), fmaxf(u[1], 0.f)};
                         o[t] = (T)u[0];
                         o[t + 1] = (T)u[1];
                     }
-                    if (!LN_ABLATE(1)) *(V8 *)(yb + out_off(hb, k)) = o;
+                    T *dst = yb + (VT ? ln_out_off<VT>(P, row, col + hb * 32) : o0 + hb * 32);
+                    if (!LN_ABLATE(1)) *(V8 *)dst = o;
                     else asm volatile("" ::"v"(o));
                 }
+            }
+    } else {
+        // ---- epilogue ---------------------------------------------------------------------------------------------------------
+        // Register r of a 32 x 32 accumulator block = column (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of row lane & 31: a lane holds
+        // 4-column groups g = r >> 2, the other half-wave holds the groups in between.  One v_permlane32_swap per register pair
+        // (g = 2k, 2k+1) exchanges them so that lanes 0-31 end up with columns 16k .. 16k+7 and lanes 32-63 with 16k+8 .. 16k+15
+        // of their row, in fp32: bias, residuals (16-byte loads, all issued before the arithmetic) and the activation are applied
+        // on 8 consecutive columns and the result leaves as one 16-byte store per lane (32 bytes of a row per instruction).
+        // (Round 2 sent the plain GEMM's results through LDS to store full 128-byte lines: qk 160 -> 152 us.  In early mode that
+        // LDS already holds the next tile's operands, and the variant is gone.)
+        V8 gv[2][2];                                                // EPI 3: the per-column LayerScale factors, packed like the bias
+        if (EPI == 3) {
+#pragma unroll
+            for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+                for (int k = 0; k < 2; ++k) gv[hb][k] = *(const V8 *)((const T *)P.gamma + cbn0 + (NH ? wc * 32 : wc * 64 + hb * 32) + hi8 + 16 * k);
         }
+        constexpr int NHB = NH ? 1 : 2;                             // W halves with results (NH: the B0 half alone)
+        const int wcol = NH ? wc * 32 : wc * 64;
+#pragma unroll
+        for (int ha = 0; ha < 2; ++ha)
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb) {
+                const int rl = ha * 64 + rb * 32 + (lane & 31);     // row inside the wave tile
+                const size_t o0 = (size_t)(cbm0 + wr * 128 + rl) * P.ldy + cbn0 + wcol + hi8;
+                // VT: where the 8 columns of piece (hb, k) go (per batch element [channels][tokens]); else o0 + hb * 32 + 16 * k
+                auto out_off = [&](const int hb_, const int k_) -> size_t {
+                    return VT ? ln_out_off<VT>(P, cbm0 + wr * 128 + rl, cbn0 + wcol + hi8 + hb_ * 32 + 16 * k_) : o0 + hb_ * 32 + 16 * k_;
+                };
+                V8 ra[2][2], rb2[2][2];                              // residual pieces [W half][k]
+                constexpr bool LNF = EPI == 4 || EPI == 5;
+                float2 st_row = {1.f, 0.f};                          // LNF, row-major output: {rstd, -mean rstd} of this lane's token
+                float cs_row = 0.f;                                  // LNF, VT: colsum of this lane's output channel
+                static_assert(!LNF || VT == 0 || VT == 1, "the folded LayerNorm exists for the row-major and the V^T store only");
+                if (LNF && VT == 0) st_row = P.ln_stats[cbm0 + wr * 128 + rl];
+                if (LNF && VT == 1) cs_row = P.ln_colsum[cbm0 + wr * 128 + rl];
+#pragma unroll
+                for (int hb = 0; hb < NHB; ++hb)
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        if (RES >= 1) ra[hb][k] = *(const V8 *)(r1 + (VT == 3 ? ln_res_off<VT>(P, cbm0 + wr * 128 + rl, cbn0 + wcol + hi8 + hb * 32 + 16 * k) : o0 + hb * 32 + 16 * k));
+                        if (RES >= 2) rb2[hb][k] = *(const V8 *)(r2 + o0 + hb * 32 + 16 * k);
+                    }
+#pragma unroll
+                for (int hb = 0; hb < NHB; ++hb)
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        float v[8];
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) {
+                            // (copies first: __builtin_bit_cast applied to a vector ELEMENT reads element 0 with this clang)
+                            const float fa = acc[ha][rb][hb][8 * k + t], fb = acc[ha][rb][hb][8 * k + 4 + t];
+                            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(fa), __float_as_uint(fb), false, false);
+                            v[t] = __uint_as_float(sw[0]);
+                            v[4 + t] = __uint_as_float(sw[1]);
+                        }
+                        V8 o;
+                        if (LNF) {                                   // fold the LayerNorm back in (fp32, before bias and activation)
+                            const int c0 = cbn0 + wcol + hi8 + hb * 32 + 16 * k;
+                            if (!VT) {
+                                const float4 s0 = *(const float4 *)(P.ln_colsum + c0), s1 = *(const float4 *)(P.ln_colsum + c0 + 4);
+                                const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+#pragma unroll
+                                for (int t = 0; t < 8; ++t) v[t] = __builtin_fmaf(v[t], st_row.x, st_row.y * sc[t]);
+                            } else {                                 // VT: the 8 columns are 8 tokens, the row is one channel
+                                const float4 *sp = (const float4 *)(P.ln_stats + c0);
+                                const float4 q0 = sp[0], q1 = sp[1], q2 = sp[2], q3 = sp[3];
+                                const float rs[8] = {q0.x, q0.z, q1.x, q1.z, q2.x, q2.z, q3.x, q3.z};
+                                const float nm[8] = {q0.y, q0.w, q1.y, q1.w, q2.y, q2.w, q3.y, q3.w};
+#pragma unroll
+                                for (int t = 0; t < 8; ++t) v[t] = __builtin_fmaf(v[t], rs[t], nm[t] * cs_row);
+                            }
+                        }
+#pragma unroll
+                        for (int t = 0; t < 8; t += 2) {
+                            lf32x2 u = {v[t] + (float)bv[hb][k][t], v[t + 1] + (float)bv[hb][k][t + 1]};
+                            if (EPI == 3) u *= (lf32x2){(float)gv[hb][k][t], (float)gv[hb][k][t + 1]};
+                            if (RES >= 1) u += (lf32x2){(float)ra[hb][k][t], (float)ra[hb][k][t + 1]};
+                            if (RES >= 2) u += (lf32x2){(float)rb2[hb][k][t], (float)rb2[hb][k][t + 1]};
+                            if (EPI == 1 || EPI == 5) u = ln_gelu2(u);
+                            if (EPI == 2) u = (lf32x2){fmaxf(u[0], 0.f), fmaxf(u[1], 0.f)};
+                            o[t] = (T)u[0];
+                            o[t + 1] = (T)u[1];
+                        }
+                        if (!LN_ABLATE(1)) *(V8 *)(yb + out_off(hb, k)) = o;
+                        else asm volatile("" ::"v"(o));
+                    }
+            }
+    }
     if (next >= nwg) break;
     orig = next;
     if (!early) {
@@ -682,6 +824,44 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
 // S = slots of the ring: 3 (72 KB: two workgroups per CU, for launches with more pieces than CUs) or 6 (144 KB, one
 // workgroup per CU with five K-tiles in flight: a piece is bound by the latency of its DMA chain, not by its 4 MFMAs per K-tile)
 #define RG_SLOT 24576            // one K-tile in LDS: x rows 0..127 (16 KB) | W rows 0..63 (8 KB)
+// The 32 x 32 block of one wave in k_linear_ragged / k_linear_thin: ONE accumulation chain per output, the chain of k_linear256's
+// dense instantiations (same instruction, same operand order, k steps ascending).  16x16x32 (LN_MF16): four 16 x 16 accumulators
+// [row block][column block], the 4 fragments of a K-tile (offA / offB) are q = 2 ks + block; piece k of the epilogue = 16-row
+// block k, the lane's 8 columns c8 as in k_linear256.  32x32x16: one accumulator, fragment q = k step q; piece k = columns 16 k ..
+#if LN_MF16
+#define LN_SMALL_ACC(m) lf32x4 m[4]; _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) m[r_ >> 2][r_ & 3] = 0.f
+#define LN_SMALL_R(m, r) m[(r) >> 2][(r) & 3]
+#define LN_SMALL_MMA(m, fb_, fa_, u0)                                                                                    \
+    _Pragma("unroll") for (int ks_ = 0; ks_ < 2; ++ks_) _Pragma("unroll") for (int b_ = 0; b_ < 4; ++b_)                 \
+        m[b_] = TR::mfma16(fb_[(u0) + 2 * ks_ + (b_ & 1)], fa_[(u0) + 2 * ks_ + (b_ >> 1)], m[b_])
+#define LN_SMALL_ROW (lane & 15)
+#define LN_SMALL_COL (16 * ((lane >> 4) & 1) + 8 * (lane >> 5))
+#define LN_SMALL_DROW(k) (16 * (k))
+#define LN_SMALL_DCOL(k) 0
+#define LN_SMALL_V(v, m, k)                                                                                              \
+    _Pragma("unroll") for (int t_ = 0; t_ < 4; ++t_) {                                                                   \
+        const float fa_ = m[2 * (k)][t_], fb_ = m[2 * (k) + 1][t_];                                                      \
+        const auto sw_ = __builtin_amdgcn_permlane16_swap(__float_as_uint(fa_), __float_as_uint(fb_), false, false);     \
+        v[t_] = __uint_as_float(sw_[0]);                                                                                 \
+        v[4 + t_] = __uint_as_float(sw_[1]);                                                                             \
+    }
+#else
+#define LN_SMALL_ACC(m) lf32x16 m; _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) m[r_] = 0.f
+#define LN_SMALL_R(m, r) m[r]
+#define LN_SMALL_MMA(m, fb_, fa_, u0) _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) m = TR::mfma(fb_[(u0) + q_], fa_[(u0) + q_], m)
+#define LN_SMALL_ROW l31
+#define LN_SMALL_COL (8 * hi)
+#define LN_SMALL_DROW(k) 0
+#define LN_SMALL_DCOL(k) (16 * (k))
+#define LN_SMALL_V(v, m, k)                                                                                              \
+    _Pragma("unroll") for (int t_ = 0; t_ < 4; ++t_) {                                                                   \
+        const float fa_ = m[8 * (k) + t_], fb_ = m[8 * (k) + 4 + t_];                                                    \
+        const auto sw_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(fa_), __float_as_uint(fb_), false, false);     \
+        v[t_] = __uint_as_float(sw_[0]);                                                                                 \
+        v[4 + t_] = __uint_as_float(sw_[1]);                                                                             \
+    }
+#endif
+#define LN_SMALL_ZERO(m) _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) LN_SMALL_R(m, r_) = 0.f
 // PIPE = 1 (deep ring only): the fragments of K-tile kt + 1 are requested BEFORE the MFMAs of K-tile kt (two register sets,
 // the loop unrolled by two), and the epilogue's operands (bias, LayerScale factor, residual rows) are requested before the
 // first DMA -- the chain "barrier -> fragment reads -> dependent MFMAs" of a K-tile loses its middle link.  Bit-identical to the
@@ -732,14 +912,16 @@ __global__ __launch_bounds__(LN_THREADS, S == 3 ? 4 : 2) void k_linear_ragged(Li
         ln_dma_s(xa_, srcA[1], sl_ + (unsigned)(2 * wid + 1) * 1024u);                                                    \
         ln_dma_s(wa_, srcB, sl_ + 16384u + (unsigned)wid * 1024u);                                                        \
     } while (0)
-    // fragment reads: lane reads LDS row l31 of its 32-row block, 16-byte slot 2 ks + hi, swizzled by the row
+    // fragment reads: lane reads LDS row l31 of its 32-row block, 16-byte slot 2 ks + hi, swizzled by the row.  16x16x32: fragment
+    // q = 2 ks + b (k step ks of 32, 16-row / 16-column block b) is LDS row 16 b + (lane & 15) of the block, slot 4 ks + (lane >> 4)
     const int br = wid >> 1, bc = wid & 1;               // this wave's 32 x 32 block of the piece: rows 32 br, columns 32 bc
     unsigned offA[4], offB[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-        const unsigned sl = (unsigned)((2 * ks + hi) ^ ((lane >> 1) & 7)) << 4;
-        offA[ks] = (unsigned)(br * 32 + l31) * 128u + sl;
-        offB[ks] = 16384u + (unsigned)(bc * 32 + l31) * 128u + sl;
+        const unsigned sl = (unsigned)((LN_MF16 ? 4 * (ks >> 1) + (lane >> 4) : 2 * ks + hi) ^ ((lane >> 1) & 7)) << 4;
+        const int lrow = LN_MF16 ? 16 * (ks & 1) + (lane & 15) : l31;
+        offA[ks] = (unsigned)(br * 32 + lrow) * 128u + sl;
+        offB[ks] = 16384u + (unsigned)(bc * 32 + lrow) * 128u + sl;
     }
     // ONE accumulation chain, the 16-wide slices of K in ascending order: exactly the chain of k_linear256's accumulators (same
     // instruction, same operand order).  Round 6: an output row's value must not depend on whether its tile falls into the main
@@ -747,22 +929,20 @@ __global__ __launch_bounds__(LN_THREADS, S == 3 ? 4 : 2) void k_linear_ragged(Li
     // image at units 0 and 31 of a batch of 32 has to come out bit-identical (rounds 3-5 ran two chains per K-tile here, even / odd
     // slices summed at the end: another fp32 order, 3.2e-3 of the depth range after 24 blocks).  Price: the four MFMAs of a K-tile
     // are dependent (~64 cycles each instead of two chains of two).
-    lf32x16 mine;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) mine[r] = 0.f;
+    LN_SMALL_ACC(mine);
 
     // epilogue operands of this wave's 32 x 32 block (see the epilogue below): with PIPE they are requested here, ahead of every
     // DMA (vmcnt retires in order: they are the oldest entries, the counted waits of the loop are unaffected)
-    const int e_row = row0 + (wid >> 1) * 32 + l31;
-    const int e_cb = col0 + (wid & 1) * 32 + 8 * hi;
+    const int e_row = row0 + (wid >> 1) * 32 + LN_SMALL_ROW;
+    const int e_cb = col0 + (wid & 1) * 32 + LN_SMALL_COL;
     V8 e_bv[2], e_gv[2], e_rv[2];
     if constexpr (PIPE) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const int col = e_cb + 16 * k;
+            const int row = e_row + LN_SMALL_DROW(k), col = e_cb + LN_SMALL_DCOL(k);
             if (P.bias) e_bv[k] = *(const V8 *)((const T *)P.bias + col);
             if (EPI == 3) e_gv[k] = *(const V8 *)((const T *)P.gamma + col);
-            if (RES >= 1) e_rv[k] = *(const V8 *)((const T *)P.res1 + ln_res_off<VT>(P, e_row, col));
+            if (RES >= 1) e_rv[k] = *(const V8 *)((const T *)P.res1 + ln_res_off<VT>(P, row, col));
         }
     }
 #pragma unroll
@@ -789,10 +969,7 @@ __global__ __launch_bounds__(LN_THREADS, S == 3 ? 4 : 2) void k_linear_ragged(Li
             RG_STAGE((kt_) + S - 1);                                                                                     \
             RG_READ(na_, nb_, (kt_) + 1);                                                                                \
             __builtin_amdgcn_sched_barrier(0);                                                                           \
-            mine = TR::mfma(cb_[0], ca_[0], mine);                                                                       \
-            mine = TR::mfma(cb_[1], ca_[1], mine);                                                                       \
-            mine = TR::mfma(cb_[2], ca_[2], mine);                                                                       \
-            mine = TR::mfma(cb_[3], ca_[3], mine);                                                                       \
+            LN_SMALL_MMA(mine, cb_, ca_, 0);                                                                             \
             __builtin_amdgcn_sched_barrier(0);                                                                           \
             LN_WAIT_LGKM0();                                                                                             \
             __builtin_amdgcn_sched_barrier(0);                                                                           \
@@ -829,10 +1006,7 @@ __global__ __launch_bounds__(LN_THREADS, S == 3 ? 4 : 2) void k_linear_ragged(Li
         __builtin_amdgcn_sched_barrier(0);
         LN_WAIT_LGKM0();
         __builtin_amdgcn_sched_barrier(0);
-        mine = TR::mfma(fb[0], fa[0], mine);
-        mine = TR::mfma(fb[1], fa[1], mine);
-        mine = TR::mfma(fb[2], fa[2], mine);
-        mine = TR::mfma(fb[3], fa[3], mine);
+        LN_SMALL_MMA(mine, fb, fa, 0);
     }
     LN_WAIT_VM(0);                                       // the trailing re-loads: nothing may still be writing LDS at exit
 #undef RG_STAGE
@@ -848,7 +1022,7 @@ __global__ __launch_bounds__(LN_THREADS, S == 3 ? 4 : 2) void k_linear_ragged(Li
         __shared__ int s_last;
         float *slot = P.rg_ws + ((size_t)q * 8 + wid) * 1024 + lane;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) __hip_atomic_store(slot + r * 64, mine[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int r = 0; r < 16; ++r) __hip_atomic_store(slot + r * 64, LN_SMALL_R(mine, r), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         LN_WAIT_VM(0);
         __syncthreads();
@@ -861,8 +1035,7 @@ __global__ __launch_bounds__(LN_THREADS, S == 3 ? 4 : 2) void k_linear_ragged(Li
         __syncthreads();
         if (!s_last) return;
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mine[r] = 0.f;
+        LN_SMALL_ZERO(mine);
         const float *first = P.rg_ws + ((size_t)(q - kpart) * 8 + wid) * 1024 + lane;
         // four (two) slots in flight per round trip, added in the order of the K ranges
         if (ksl >= 2) {
@@ -876,7 +1049,7 @@ __global__ __launch_bounds__(LN_THREADS, S == 3 ? 4 : 2) void k_linear_ragged(Li
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) mine[r] += part[u][r];
+                    for (int r = 0; r < 16; ++r) LN_SMALL_R(mine, r) += part[u][r];
             }
         } else {
             float part[2][16];
@@ -888,20 +1061,18 @@ __global__ __launch_bounds__(LN_THREADS, S == 3 ? 4 : 2) void k_linear_ragged(Li
 #pragma unroll
             for (int u = 0; u < 2; ++u)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) mine[r] += part[u][r];
+                for (int r = 0; r < 16; ++r) LN_SMALL_R(mine, r) += part[u][r];
         }
     }
 
-    // ---- epilogue of block wid = (32-row block wid >> 1, 32-column block wid & 1), as in k_linear256: register r = column
-    // (r & 3) + 8 (r >> 2) + 4 hi of row l31; one permlane32 swap per register pair gives each lane 8 consecutive columns
-    const int row = row0 + (wid >> 1) * 32 + l31;
-    const int cb = col0 + (wid & 1) * 32 + 8 * hi;
+    // ---- epilogue of block wid = (32-row block wid >> 1, 32-column block wid & 1), as in k_linear256: 8 consecutive columns of
+    // one row per lane and piece k (LN_SMALL_V)
     T *yb = (T *)P.y;
     const T *bias = (const T *)P.bias;
     const T *r1 = (const T *)P.res1;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const int col = cb + 16 * k;
+        const int row = e_row + LN_SMALL_DROW(k), col = e_cb + LN_SMALL_DCOL(k);
         const size_t off = ln_out_off<VT>(P, row, col);
         V8 bv, gv, rv;
         if (bias) bv = PIPE ? e_bv[k] : *(const V8 *)(bias + col);
@@ -912,13 +1083,7 @@ __global__ __launch_bounds__(LN_THREADS, S == 3 ? 4 : 2) void k_linear_ragged(Li
         if (EPI == 3) gv = PIPE ? e_gv[k] : *(const V8 *)((const T *)P.gamma + col);
         if (RES >= 1) rv = PIPE ? e_rv[k] : *(const V8 *)(r1 + ln_res_off<VT>(P, row, col));
         float v[8];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const float fa = mine[8 * k + t], fb = mine[8 * k + 4 + t];
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(fa), __float_as_uint(fb), false, false);
-            v[t] = __uint_as_float(sw[0]);
-            v[4 + t] = __uint_as_float(sw[1]);
-        }
+        LN_SMALL_V(v, mine, k);
         if (EPI == 4 || EPI == 5) {                          // the folded LayerNorm, as in k_linear256
             if (!VT) {
                 const float2 st = P.ln_stats[row];
@@ -1005,28 +1170,27 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear_thin(LinParams P)
         ln_dma_s(wa_, srcB[1], sl_ + 8192u + (unsigned)(2 * wid + 1) * 1024u);                                            \
     } while (0)
     const bool mw = wid < 2;                             // the two waves that multiply: columns 32 wid .. 32 wid + 31 of the piece
-    unsigned offA[8], offB[8];
+    unsigned offA[8], offB[8];           // fragment u = 4 j + q of a step: K-tile j, fragment q as in k_linear_ragged
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const int j = u >> 2, ks = u & 3;
-        const unsigned sl = (unsigned)((2 * ks + hi) ^ ((lane >> 1) & 7)) << 4;
-        offA[u] = (unsigned)j * 4096u + (unsigned)l31 * 128u + sl;
-        offB[u] = 8192u + (unsigned)j * 8192u + (unsigned)((wid & 1) * 32 + l31) * 128u + sl;
+        const unsigned sl = (unsigned)((LN_MF16 ? 4 * (ks >> 1) + (lane >> 4) : 2 * ks + hi) ^ ((lane >> 1) & 7)) << 4;
+        const int lrow = LN_MF16 ? 16 * (ks & 1) + (lane & 15) : l31;
+        offA[u] = (unsigned)j * 4096u + (unsigned)lrow * 128u + sl;
+        offB[u] = 8192u + (unsigned)j * 8192u + (unsigned)((wid & 1) * 32 + lrow) * 128u + sl;
     }
-    lf32x16 mine;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) mine[r] = 0.f;
+    LN_SMALL_ACC(mine);
     // epilogue operands first (the oldest vmcnt entries: the counted waits of the loop are unaffected)
-    const int e_row = row0 + l31;
-    const int e_cb = col0 + (wid & 1) * 32 + 8 * hi;
+    const int e_row = row0 + LN_SMALL_ROW;
+    const int e_cb = col0 + (wid & 1) * 32 + LN_SMALL_COL;
     V8 e_bv[2], e_gv[2], e_rv[2];
     if (mw) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const int col = e_cb + 16 * k;
+            const int row = e_row + LN_SMALL_DROW(k), col = e_cb + LN_SMALL_DCOL(k);
             if (P.bias) e_bv[k] = *(const V8 *)((const T *)P.bias + col);
             if (EPI == 3) e_gv[k] = *(const V8 *)((const T *)P.gamma + col);
-            if (RES >= 1) e_rv[k] = *(const V8 *)((const T *)P.res1 + (size_t)e_row * P.ldy + col);
+            if (RES >= 1) e_rv[k] = *(const V8 *)((const T *)P.res1 + (size_t)row * P.ldy + col);
         }
     }
 #pragma unroll
@@ -1050,7 +1214,8 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear_thin(LinParams P)
         if (mw) {                                                                                                        \
             TH_READ(na_, nb_, (st_) + 1);                                                                                \
             __builtin_amdgcn_sched_barrier(0);                                                                           \
-            _Pragma("unroll") for (int u = 0; u < 8; ++u) mine = TR::mfma(cb_[u], ca_[u], mine);                         \
+            LN_SMALL_MMA(mine, cb_, ca_, 0);                                                                             \
+            LN_SMALL_MMA(mine, cb_, ca_, 4);                                                                             \
             __builtin_amdgcn_sched_barrier(0);                                                                           \
             LN_WAIT_LGKM0();                                                                                             \
             __builtin_amdgcn_sched_barrier(0);                                                                           \
@@ -1077,11 +1242,10 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear_thin(LinParams P)
     if (!mw) return;
 
     // ---- epilogue of this wave's 32 x 32 block, as in k_linear_ragged (VT 0)
-    const int row = e_row, cb = e_cb;
     T *yb = (T *)P.y;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const int col = cb + 16 * k;
+        const int row = e_row + LN_SMALL_DROW(k), col = e_cb + LN_SMALL_DCOL(k);
         const size_t off = (size_t)row * P.ldy + col;
         V8 bv;
         if (P.bias) bv = e_bv[k];
@@ -1090,13 +1254,7 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear_thin(LinParams P)
             for (int t = 0; t < 8; ++t) bv[t] = (T)0.f;
         }
         float v[8];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const float fa = mine[8 * k + t], fb = mine[8 * k + 4 + t];
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(fa), __float_as_uint(fb), false, false);
-            v[t] = __uint_as_float(sw[0]);
-            v[4 + t] = __uint_as_float(sw[1]);
-        }
+        LN_SMALL_V(v, mine, k);
         if (EPI == 4 || EPI == 5) {                          // the folded LayerNorm, as in k_linear256
             const float2 stt = P.ln_stats[row];
             const float4 s0 = *(const float4 *)(P.ln_colsum + col), s1 = *(const float4 *)(P.ln_colsum + col + 4);

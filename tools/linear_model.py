@@ -5,6 +5,8 @@
    half-tile may be re-staged before every read of its previous content was retired behind a barrier.
 2. `check_indexing()` -- the address arithmetic (source swizzle of the DMA, LDS image, swizzled fragment reads, MFMA
    32x32x16 operand/accumulator layout, epilogue) executed with numpy for one workgroup; must equal x @ W.T.
+3. `check_indexing16()`, `bank_conflicts16()` -- the same for the 16x16x32 chain of the dense instantiations (16 x 32
+   fragments, permlane16_swap epilogue).
 
     python tools/linear_model.py
 """
@@ -245,6 +247,108 @@ def bank_conflicts():
     return worst
 
 
+# ---- 3. the 16x16x32 chain of the dense instantiations -----------------------------------------------------------------
+# Same LDS image and schedule (check_schedule, stage); a fragment is now 16 rows x 32 k: lane l reads LDS row (l & 15) of its
+# 16-row block at logical slot 4 ks + (l >> 4), k step ks = 0, 1 of the K-tile.
+
+def frag16_offset(kind, s, wr, wc, blk, ks, lane):
+    """byte offset of lane's ds_read_b128 for fragment (16-row / 16-column block blk, k step ks) of half-tile kind"""
+    h = int(kind[1])
+    sl = ((4 * ks + (lane >> 4)) ^ ((lane >> 1) & 7)) << 4
+    if kind[0] == 'A':
+        return (wr * 64 + (lane & 15)) * 128 + sl + h * 2 * LN_HALF + s * LN_HALF + blk * 2048
+    return LN_B_BASE + (wc * 32 + (lane & 15)) * 128 + sl + h * 2 * LN_HALF + s * LN_HALF + blk * 2048
+
+
+def read_frag16(lds, kind, s, wr, wc, blk, ks):
+    out = np.empty((64, 8), lds.dtype)
+    for lane in range(64):
+        off = frag16_offset(kind, s, wr, wc, blk, ks, lane)
+        out[lane] = lds[off // 2: off // 2 + 8]
+    return out
+
+
+def mfma_16x16x32(a, b, c):
+    """v_mfma_f32_16x16x32: a, b [64, 8]; lane l holds A[m = l&15][k = 8 (l>>4) + t], B[k][n = l&15];
+    c [64, 4]: lane l, register r holds D[m = 4 (l>>4) + r][n = l&15]."""
+    A = np.zeros((16, 32)); B = np.zeros((32, 16))
+    for l in range(64):
+        for t in range(8):
+            A[l & 15, 8 * (l >> 4) + t] = a[l, t]
+            B[8 * (l >> 4) + t, l & 15] = b[l, t]
+    D = A @ B
+    out = c.copy()
+    for l in range(64):
+        for r in range(4):
+            out[l, r] += D[4 * (l >> 4) + r, l & 15]
+    return out
+
+
+def permlane16_swap(vdst, src):
+    """v_permlane16_swap: the odd 16-lane rows of vdst are exchanged with the even rows of src; returns (vdst, src)"""
+    d, s_ = vdst.copy(), src.copy()
+    for row in (0, 2):
+        lo, hi = slice(16 * row, 16 * row + 16), slice(16 * row + 16, 16 * row + 32)
+        d[hi], s_[lo] = src[lo], vdst[hi]
+    return d, s_
+
+
+def epilogue_cols16(lane):
+    """the 8 columns a lane holds after the swap, inside a 32-column W half"""
+    g = lane >> 4
+    return 16 * (g & 1) + 8 * (g >> 1)
+
+
+def check_indexing16(M=300, N=256, K=128, seed=0):
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((M, K)).astype(np.float32)
+    w = rng.standard_normal((N, K)).astype(np.float32)
+    y = np.full((M, N), np.nan)
+    nt = K // 64
+    for bm0 in [min(p0, M - 256) for p0 in range(0, M, 256)]:
+        for bn0 in range(0, N, 256):
+            lds = np.zeros(131072 // 2, np.float32)
+            for wr in range(2):
+                for wc in range(4):
+                    acc = np.zeros((2, 4, 2, 2, 64, 4))           # [x half][row block][W half][column block]
+                    for kt in range(nt):
+                        s = kt & 1
+                        for kind in ('A0', 'A1', 'B0', 'B1'):
+                            stage(lds, kind, kt, s, x, w, bm0, bn0, M, K)
+                        for ha in range(2):
+                            for hb in range(2):
+                                for ks in range(2):
+                                    for rb in range(4):
+                                        fa = read_frag16(lds, 'A%d' % ha, s, wr, wc, rb, ks)
+                                        for cb in range(2):
+                                            fb = read_frag16(lds, 'B%d' % hb, s, wr, wc, cb, ks)
+                                            acc[ha, rb, hb, cb] = mfma_16x16x32(fb, fa, acc[ha, rb, hb, cb])
+                    for ha in range(2):
+                        for rb in range(4):
+                            for hb in range(2):
+                                lo, hi = permlane16_swap(acc[ha, rb, hb, 0], acc[ha, rb, hb, 1])
+                                for lane in range(64):
+                                    m = bm0 + wr * 128 + ha * 64 + rb * 16 + (lane & 15)
+                                    n0 = bn0 + wc * 64 + hb * 32 + epilogue_cols16(lane)
+                                    y[m, n0:n0 + 8] = np.concatenate([lo[lane], hi[lane]])
+    ref = x.astype(np.float64) @ w.astype(np.float64).T
+    return np.abs(y - ref).max()                             # NaN if an output was never written
+
+
+def bank_conflicts16():
+    """the 16x16x32 fragment reads of k_linear256, k_linear_ragged and k_linear_thin: every 16-lane group must hit 16 distinct
+    16-byte slots of the 256-byte bank row (row offsets of the blocks are multiples of 2048 bytes: the pattern of block 0)"""
+    worst = 0
+    for ks in range(2):
+        for grp in range(4):
+            slots = set()
+            for lane in range(16 * grp, 16 * grp + 16):
+                off = frag16_offset('A0', 0, 0, 0, 0, ks, lane)
+                slots.add((off % 256) // 16)
+            worst = max(worst, 16 - len(slots))
+    return worst
+
+
 if __name__ == '__main__':
     for nt in (2, 4, 6, 16, 64):
         p = check_schedule(nt)
@@ -252,3 +356,4 @@ if __name__ == '__main__':
     print('bank conflicts (missing slots per 16-lane group):', bank_conflicts())
     print('indexing max |err|:', check_indexing())
     print('convolution gather max |err|:', check_conv_indexing())
+    print('16x16x32: bank conflicts', bank_conflicts16(), '| indexing max |err|:', check_indexing16())
