@@ -228,7 +228,7 @@ int ds_convert_to_i16(ds_ctx *ctx, const void *arr, int is_f64, int64_t count, u
 /* element types of the tensor-core entry points */
 #define DS_DTYPE_F16  1
 #define DS_DTYPE_BF16 2
-#define DS_DTYPE_F32  3       /* ds_preprocess_bicubic only */
+#define DS_DTYPE_F32  3       /* ds_preprocess_bicubic and ds_dwconv_nhwc only */
 
 /*
  * ds_attention_fwd -- fused attention forward of one transformer block; replaces the q@k^T -> (+bias) -> softmax -> @v
@@ -502,6 +502,23 @@ int ds_add_relu_f32(ds_ctx *ctx, const float *a, const float *b, float *y, int64
  */
 int ds_bias_act_f32(ds_ctx *ctx, const float *x, const float *bias, const float *res, float *y, int64_t pixels, int channels, int relu,
                     void *stream);
+
+/*
+ * ds_dwconv_nhwc -- the depthwise convolution of an EfficientNet-Lite block with the element-wise tails on both sides, one pass: the
+ * 24 depthwise convolutions of MiDaS v2.1 small (model id 6; dmidas/midas_net_custom.py:12-67 on gen-efficientnet's
+ * tf_efficientnet_lite3, dmidas/blocks.py:169-189) -- InvertedResidual `conv_pw -> bn1 -> act1 -> conv_dw -> bn2 -> act2` from the
+ * second step on, and DepthwiseSeparableConv `conv_dw -> bn1 -> act1` with the stem's `bn1 -> act1` in front (BatchNorm folded):
+ *     a(n, iy, ix, c) = min(max(x[n, iy, ix, c] + bias_in[c], 0), 6) inside the image, 0 outside (zero padding of the ACTIVATED x)
+ *     y[n, oy, ox, c] = min(max(bias[c] + sum_{ky,kx} w[ky * kernel + kx][c] * a(n, oy * stride - pad_top + ky,
+ *                                                                               ox * stride - pad_left + kx, c), 0), 6)
+ * x [batch, in_h, in_w, channels], y [batch, out_h, out_w, channels]: channels_last, f16 or f32; w [kernel * kernel][channels] float32
+ * (the folded weight, tap-major), bias_in / bias [channels] float32.  kernel 3 or 5, stride 1 or 2, 0 <= pad_top, pad_left < kernel;
+ * the bottom / right padding follows from out_h / out_w and lies in (-stride, kernel).  channels % 8 == 0, operands 16-byte aligned,
+ * y must not alias x (DS_EINVAL otherwise; bf16: DS_EUNSUPPORTED).  fp32 accumulation in ky-major tap order, + bias, one rounding to
+ * the output type: an image's output does not depend on the batch size or on its position in the batch.  No workspace.
+ */
+int ds_dwconv_nhwc(ds_ctx *ctx, const void *x, const float *w, const float *bias_in, const float *bias, void *y, int batch, int in_h,
+                   int in_w, int channels, int out_h, int out_w, int kernel, int stride, int pad_top, int pad_left, int dtype, void *stream);
 int ds_relu_cat_f32(ds_ctx *ctx, const float *a, const float *b, float *y, int batch, int64_t plane, int channels_a, int channels_b, int layout,
                     void *stream);
 

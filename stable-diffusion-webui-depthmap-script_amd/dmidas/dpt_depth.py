@@ -188,6 +188,9 @@ class DPTDepthModel(DPT):
             return _native.preprocess_bicubic(images_u8, (nh, nw), mean, std, flip=True, dtype=dtype)
         x = images_u8.flip(-1).permute(0, 3, 1, 2).float() / 255.0
         x = F.interpolate(x, size=(nh, nw), mode="bicubic", align_corners=False)
+        if hasattr(mean, "__len__"):                     # per-channel statistics (ImageNet: MiDaS v2.1 small), channel 0 first
+            mean = vm.device_constant(mean, x.device).view(1, 3, 1, 1)
+            std = vm.device_constant(std, x.device).view(1, 3, 1, 1)
         x = (x - mean) / std
         return x if dtype is None else x.to(dtype)
 

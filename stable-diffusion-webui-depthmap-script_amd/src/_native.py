@@ -25,6 +25,7 @@ EXPORTS = [
     "ds_convert_to_i16", "ds_profile_enable", "ds_profile_last_ms", "ds_stereo_last_stats", "ds_attention_fwd", "ds_attention_bias_pack", "ds_colorize_u16", "ds_residual_layernorm", "ds_boost_blend", "ds_upsample_bilinear_nhwc", "ds_dpt_head_tail", "ds_preprocess_bicubic", "ds_linear_reload_env", "ds_attention_reload_env", "ds_normalmap_selfcheck", "ds_normalmap_gradient_f16", "ds_normalmap_gradient_blur_f32",
     "ds_linear_shuffle", "ds_linear_readout", "ds_kernel_timer_enable", "ds_kernel_timer_read", "ds_kernel_timer_read_each", "ds_group_norm_nchw",
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
+    "ds_dwconv_nhwc",
 ]
 
 
@@ -99,6 +100,7 @@ def lib():
             L.ds_add_relu_f32.argtypes = [vp, vp, vp, vp, i64, vp]
             L.ds_bias_act_f32.argtypes = [vp, vp, vp, vp, vp, i64, ci, ci, vp]
             L.ds_relu_cat_f32.argtypes = [vp, vp, vp, vp, ci, i64, ci, ci, ci, vp]
+            L.ds_dwconv_nhwc.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]
             L.ds_kernel_timer_enable.argtypes = [vp, ci]
             L.ds_kernel_timer_read.argtypes = [vp, ci, ctypes.POINTER(i64), ctypes.POINTER(cd)]
             L.ds_kernel_timer_read_each.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_float), i64, ctypes.POINTER(i64)]
@@ -663,6 +665,24 @@ def relu_cat_f32(a, b):
     out = torch.empty((n, ca + cb, h, w), dtype=a.dtype, device=a.device, memory_format=torch.channels_last if lay == 0 else torch.contiguous_format)
     CALLS["ds_relu_cat_f32"] += 1
     _check(lib().ds_relu_cat_f32(ctx_for(_dev_index(a)), a.data_ptr(), b.data_ptr(), out.data_ptr(), n, h * w, ca, cb, lay, _stream(a)))
+    return out
+
+
+def dwconv(x, w_taps, bias_in, bias, kernel, stride, pad_top, pad_left, out_hw):
+    """relu6(bias + depthwise_conv(relu6(x + bias_in), w)) for a float16 / float32 CUDA activation, channels_last in and out
+    (include/depthstereo.h: ds_dwconv_nhwc): the padding (pad_top / pad_left before, what out_hw implies after) is applied to the
+    ACTIVATED x.  w_taps [kernel * kernel, C] float32 (tap-major), bias_in / bias [C] float32.  Returns [B, C, out_h, out_w]."""
+    torch = require_gpu()
+    assert x.is_cuda and x.dtype in (torch.float16, torch.float32) and x.dim() == 4
+    x = x.contiguous(memory_format=torch.channels_last)
+    b, c, h, w = x.shape
+    for t, n in ((w_taps, kernel * kernel * c), (bias_in, c), (bias, c)):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    out = torch.empty((b, c, int(out_hw[0]), int(out_hw[1])), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    CALLS["ds_dwconv_nhwc"] += 1
+    _check(lib().ds_dwconv_nhwc(ctx_for(_dev_index(x)), x.data_ptr(), w_taps.data_ptr(), bias_in.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                b, h, w, c, out.shape[2], out.shape[3], int(kernel), int(stride), int(pad_top), int(pad_left),
+                                1 if x.dtype == torch.float16 else 3, _stream(x)))
     return out
 
 

@@ -218,7 +218,7 @@ def _single_estimates(patches, msize, net, model_type, chunk):
             u8 = (p * 255.1).clamp(0, 255).to(torch.uint8).flip(-1)    # (:550) the second channel swap; net swaps again
             outs.append(net.infer_batch(u8.unsqueeze(0), int(msize))[0])
         return outs
-    if model_type in (1, 2, 3, 4):                           # estimatemidasBoost (:1180-1220)
+    if model_type in (1, 2, 3, 4, 6):                        # estimatemidasBoost (:1180-1220)
         from dmidas.dpt_depth import midas_net_size
         mean = vm.device_constant(vm.IMAGENET_MEAN, dev).view(1, 3, 1, 1)      # ImageNet statistics for EVERY MiDaS
         std = vm.device_constant(vm.IMAGENET_STD, dev).view(1, 3, 1, 1)       # model here, unlike estimatemidas
@@ -240,7 +240,7 @@ def _single_estimates(patches, msize, net, model_type, chunk):
             u8 = (p * 255).to(torch.uint8)                   # truncation like np.uint8; no channel swap on this path
             outs.append(net.infer_batch(u8.unsqueeze(0), int(msize), int(msize))[0])
         return outs
-    raise NotImplementedError(f"Boost with depth model id {model_type} is not built (built: 0 LeReS, 1-4 MiDaS DPT, 7-9 ZoeDepth, "
+    raise NotImplementedError(f"Boost with depth model id {model_type} is not built (built: 0 LeReS, 1-4 MiDaS DPT, 6 MiDaS v2.1 small, 7-9 ZoeDepth, "
                               "12-14 Depth-Anything-V2)")
 
 

@@ -224,7 +224,7 @@ def _postprocess_batch(pred, invert, inp):
 
 def _wants_reference_f16():
     """`reference_f16_postproc` (ops / ModelHolder.update_settings; DS_REFERENCE_F16_POSTPROC=1): reproduce the reference's
-    float16 depth post-processing for the networks whose prediction it receives as a float16 array (MiDaS ids 1-4 in half
+    float16 depth post-processing for the networks whose prediction it receives as a float16 array (MiDaS ids 1-4 and 6 in half
     precision: src/depthmap_generation.py:268-275, :484-497).  DEFAULT OFF -- a defined corner, see DESIGN.md: by default a
     half-precision network's prediction is post-processed in float32 here (65 536 depth levels instead of float16's ~2 k per
     octave)."""
@@ -238,7 +238,7 @@ def _wants_reference_f16():
         return False
     if getattr(dm, "returns_f16", False):                    # a registered predictor that says so
         return True
-    return getattr(dm, "model_type", None) in (1, 2, 3, 4) and not getattr(dm, "no_half", True)
+    return getattr(dm, "model_type", None) in (1, 2, 3, 4, 6) and not getattr(dm, "no_half", True)
 
 
 def _postprocess_f16(pred, invert, inp):

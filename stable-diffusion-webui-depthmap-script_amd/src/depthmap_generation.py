@@ -6,13 +6,15 @@ the reference.  Built model families:
     id  0           LeReS res101 (ResNeXt101-32x8d)      (lib.multi_depth_model_woauxi.RelDepthModel; reference :101-114)
     ids 1, 2        MiDaS 3.1 DPT BEiT-L/16 512 / 384   (dmidas.dpt_depth.DPTDepthModel; reference :116-146)
     ids 3, 4        MiDaS 3.0 dpt_large_384 (ViT-L/16) / dpt_hybrid_384 (ViT-B/16 + ResNetV2-50 stem)   (reference :147-170)
+    id  6           MiDaS v2.1 small (EfficientNet-Lite3)   (dmidas.midas_net_custom.MidasNet_small; reference :182-193)
     ids 7, 8, 9     ZoeDepth N / K / NK on the DPT BEiT-L/16 384 core   (dzoedepth.zoedepth; reference :196-209, :443-452)
     ids 12, 13, 14  Depth-Anything-V2 small/base/large   (ddepth_anything_v2.DepthAnythingV2; reference :237-248)
 Checkpoints are looked up in ``model_dir`` under the reference's file names; the reference downloads them when missing
 (ensure_file_downloaded) -- this build has no network path and raises FileNotFoundError instead, unless
 ``allow_random_init`` is set (bench / tests: random weights of the same architecture).
-Other ids (midas_v21 5-6, Marigold 10, Depth-Anything v1 11: their networks are not vendored by the reference) are
-not built: ``ensure_models`` raises NotImplementedError unless a predictor was registered with ``register_predictor``.
+Other ids (midas_v21 5: a ResNeXt-101-WSL encoder; Marigold 10 and Depth-Anything v1 11: their networks are not vendored by
+the reference) are not built: ``ensure_models`` raises NotImplementedError unless a predictor was registered with
+``register_predictor``.
 Boost (``boost=True``; src/boost.py + the pix2pix merge network + ds_boost_blend) runs on every built base model.
 Nothing ever falls back silently.
 """
@@ -57,9 +59,15 @@ def _build_leres():
     return RelDepthModel(backbone='resnext101'), "res101.pth"
 
 
+def _build_midas_small():
+    from dmidas.midas_net_custom import MidasNet_small
+    return (MidasNet_small(path=None, features=64, backbone="efficientnet_lite3", exportable=True, non_negative=True, blocks={'expand': True}),
+            "midas_v21_small-70d6b9c8.pt")
+
+
 _BUILDERS = {0: _build_leres, 1: _build_dpt_beit("beitl16_512", "dpt_beit_large_512.pt"), 2: _build_dpt_beit("beitl16_384", "dpt_beit_large_384.pt"),
              3: _build_dpt_beit("vitl16_384", "dpt_large-midas-2f21e586.pt"), 4: _build_dpt_beit("vitb_rn50_384", "dpt_hybrid-midas-501f0c75.pt"),
-             7: _build_zoe("zoedepth_n"), 8: _build_zoe("zoedepth_k"), 9: _build_zoe("zoedepth_nk"),
+             6: _build_midas_small, 7: _build_zoe("zoedepth_n"), 8: _build_zoe("zoedepth_k"), 9: _build_zoe("zoedepth_nk"),
              12: _build_dav2('s'), 13: _build_dav2('b'), 14: _build_dav2('l')}
 
 
@@ -169,6 +177,10 @@ class _NetPredictor:
             return self.net.infer_batch(batch, int(net_width), int(net_height))      # estimatezoedepth (:443-452)
         if self.is_dav2:
             return self.net.infer_batch(batch, int(net_width))             # reference passes net_width as input_size (:553)
+        if self.model_type == 6:                                            # midas_v21_small: upper_bound, ImageNet statistics (:182-193)
+            from .vit_mi355x import IMAGENET_MEAN, IMAGENET_STD
+            return self.net.infer_batch(batch, net_size=int(net_width), resize_mode="upper_bound", net_h=int(net_height),
+                                        mean=IMAGENET_MEAN, std=IMAGENET_STD)
         mode = "minimal"                                                    # resize_mode of ids 1-4 (:127, :141, :155, :168)
         return self.net.infer_batch(batch, net_size=int(net_width), resize_mode=mode, net_h=int(net_height))
 
@@ -202,9 +214,9 @@ class ModelHolder:
         from . import miopen_db
         miopen_db.seed()                 # the package's MIOpen find results, before the first library convolution (src/miopen_db.py)
         if boost:
-            if model_type not in (0, 1, 2, 3, 4, 7, 8, 9, 12, 13, 14):
+            if model_type not in (0, 1, 2, 3, 4, 6, 7, 8, 9, 12, 13, 14):
                 raise NotImplementedError(f"Boost with depth model id {model_type!r} is not built (built: 0 LeReS, 1-4 MiDaS "
-                                          "DPT, 7-9 ZoeDepth, 12-14 Depth-Anything-V2)")
+                                          "DPT, 6 MiDaS v2.1 small, 7-9 ZoeDepth, 12-14 Depth-Anything-V2)")
             if self.pix2pix_model is None:
                 self.pix2pix_model = _load_pix2pix(device, self.allow_random_init)
         else:
