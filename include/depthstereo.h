@@ -265,9 +265,10 @@ int ds_attention_bias_pack(ds_ctx *ctx, const float *bias, int H, int n, int Np,
 
 /*
  * ds_attention_reload_env -- ds_attention_fwd reads its A/B switches (DS_ATT_GEN = 2 / 4: kernel generation -- generation 4 runs
- * one wave per SIMD with two query sub-blocks skewed inside the wave, generation 2, the default, two or three waves per SIMD;
+ * one wave per SIMD with two query sub-blocks skewed inside the wave, generation 2, the default, two to four waves per SIMD;
  * DS_ATT_TAIL = 0 / 1: query blocks with at most four live rows as GEMVs instead of tiles; DS_ATT_NQB, DS_ATT_LATE, DS_ATT_ORDER)
- * once per process; this call reads them again.  Every setting computes the same function (dmidas/backbones/beit.py:65-91);
+ * once per process; this call reads them again.  These five are all the switches there are: generations 1 and 3, the ablation
+ * masks and the phase clock were removed from the library.  Every setting computes the same function (dmidas/backbones/beit.py:65-91);
  * generations 2 and 4 are bit-identical with DS_ATT_TAIL = 0.  Tests and A/B runs only.
  */
 int ds_attention_reload_env(void);

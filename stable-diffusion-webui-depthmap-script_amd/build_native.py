@@ -26,9 +26,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fn
 
 
 if EXPERIMENTS:
-    # timing ablations, superseded kernel generations and kernels that have not run on hardware yet (DS_ATT_ABLATE, DS_ATT_V1,
-    # DS_ATT_GEN=3, DS_LIN_ABLATE, DS_PL_DEBUG ...): some of them produce WRONG results by design, so they are compiled only on
-    # request, into a library of their own, never into the default one
+    # timing ablations and kernels that have not run on hardware yet (DS_LIN_ABLATE, DS_PL_DEBUG ...): some of them produce WRONG
+    # results by design, so they are compiled only on request, into a library of their own, never into the default one
     FLAGS.append("-DDS_EXPERIMENTS")
 
 

@@ -11,11 +11,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 #define AT_THREADS 256
-#define AT_QW 32                 // query rows per wave
-#define AT_QB (AT_QW * 4)        // query rows per workgroup
+#define AT_QB 128                // query rows per workgroup at 32 rows per wave (the grid-size bound of ds_attention_fwd)
 #define AT_KB 64                 // keys per tile
 #define AT_D 64
-#define AT_VROW 136              // bytes per V^T row in LDS (128 + 8 pad)
 
 template <int BF16> struct at_traits;
 template <> struct at_traits<0> {
@@ -24,12 +22,6 @@ template <> struct at_traits<0> {
     static __device__ __forceinline__ f32x16 mfma(V8 a, V8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ T from_f32(float x) { return (_Float16)x; }
     static __device__ __forceinline__ float to_f32(T x) { return (float)x; }
-    // acc + a[i] + a[i+1]: v_dot2_f32_f16 against (1, 1)
-    static __device__ __forceinline__ float add2(V8 a, int i, float acc) {
-        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        const h2 v = { a[i], a[i + 1] }, one = { (_Float16)1.0f, (_Float16)1.0f };
-        return __builtin_amdgcn_fdot2(v, one, acc, false);
-    }
 };
 template <> struct at_traits<1> {
     typedef __bf16 T; typedef bf16x8 V8;
@@ -37,7 +29,6 @@ template <> struct at_traits<1> {
     static __device__ __forceinline__ f32x16 mfma(V8 a, V8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ T from_f32(float x) { return (__bf16)x; }
     static __device__ __forceinline__ float to_f32(T x) { return (float)x; }
-    static __device__ __forceinline__ float add2(V8 a, int i, float acc) { return acc + ((float)a[i] + (float)a[i + 1]); }
 };
 
 // row of the 32x32 accumulator held in register r of a lane with hi = lane >> 5 (cdna_hip_programming.md, 3. MFMA)
@@ -47,11 +38,12 @@ struct AttnParams {
     const void *qk, *vt, *bias;
     void *out;
     int B, Np, H, n_valid;
-    int flags;                   // bit 0: wave priority around the MFMA clusters (generation 1), 2: batch-fastest work order, 4: tail blocks as GEMVs
+    int flags;                   // 2: batch-fastest work order, 4: tail blocks as GEMVs (bit 0 is not used)
     int nq, total, chunk;        // query blocks per (b,h); B*H*nq; ceil(total / 8) (XCD-aware work order, see the kernel)
-    float k_logit;               // scale*log2(e): with a bias, the factor of the raw accumulator in  x = s*k_logit + bias
-    float c_exp;                 // factor inside the exponent, p = exp2((x - max x)*c_exp): scale*log2(e) without a bias,
-                                 // 1 with one (the packed bias is in log2 units)
+    float unused;                // read by nothing (generation 1's logit factor).  Kept because c_exp's offset in the kernel
+                                 // argument block decides the compiler's scalar register assignment in every kernel
+    float c_exp;                 // factor inside the exponent, p = exp2((x - max x)*c_exp): scale*log2(e); x = q.k + bias/scale
+                                 // (the packed bias is stored in units of 1/scale)
 };
 
 

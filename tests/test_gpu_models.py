@@ -44,15 +44,9 @@ def test_attention_kernel_matches_definition(gpu, dtype, with_bias):
             lane = torch.arange(64, device='cuda')
             c = torch.arange(4, device='cuda')
             j = torch.arange(8, device='cuda')
-            if os.environ.get("DS_ATT_V1"):       # first kernel generation: register order of the logits tile, log2 units
-                r = 8 * (c[:, None, None] & 1) + j[None, None, :]
-                key = ((c[:, None, None] >> 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane[None, :, None] >> 5)).expand(4, 64, 8)
-                qq = (lane & 31)[None, :, None].expand(4, 64, 8)
-                mul = vm.LOG2E
-            else:
-                qq = (16 * (c[:, None, None] & 1) + 8 * (lane[None, :, None] >> 5) + j[None, None, :]).expand(4, 64, 8)
-                key = (32 * (c[:, None, None] >> 1) + (lane & 31)[None, :, None]).expand(4, 64, 8)
-                mul = 8.0
+            qq = (16 * (c[:, None, None] & 1) + 8 * (lane[None, :, None] >> 5) + j[None, None, :]).expand(4, 64, 8)
+            key = (32 * (c[:, None, None] >> 1) + (lane & 31)[None, :, None]).expand(4, 64, 8)
+            mul = 8.0
             for qb in (0, npad // 32 - 1):
                 for kt in (0, npad // 64 - 1):
                     exact = (padded[:, qb * 32:(qb + 1) * 32, kt * 64:(kt + 1) * 64] * mul)[:, qq, key]
@@ -550,7 +544,7 @@ GOLD_LARGE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", 
     (1, 577, 12, False, torch.float16),       # dpt_hybrid_384 (BASELINE config 2)
 ])
 def test_attention_kernel_at_benchmark_shapes(gpu, b, n_valid, h, with_bias, dtype):
-    """k_attention_fwd against its float32 definition (vit_mi355x.attention_reference, query-tiled so the B x H x N x N
+    """k_attention_fwd2 against its float32 definition (vit_mi355x.attention_reference, query-tiled so the B x H x N x N
     logits never exceed 1 GiB) at the exact launch shapes of the networks BASELINE.json names -- every batch element,
     every head, every valid row.  dmidas/backbones/beit.py:65-91, dinov2_layers/attention.py:49-62."""
     from src import vit_mi355x as vm

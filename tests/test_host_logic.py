@@ -479,7 +479,7 @@ def test_bench_line_in_step_figures_agree_with_the_committed_trace():
 def test_standalone_harnesses_compile(tmp_path):
     """tools/att_harness.cpp and tools/stereo_harness.cpp (the Python-free A/B harnesses of the GPU rounds) keep compiling
     against the HIP runtime and use the C ABI's current signatures by name (dlsym): every symbol they ask for is declared in
-    include/depthstereo.h, except the experiments-only profile reader."""
+    include/depthstereo.h."""
     import shutil
     import subprocess
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -490,7 +490,7 @@ def test_standalone_harnesses_compile(tmp_path):
         src = os.path.join(conftest.ROOT, "tools", name + ".cpp")
         text = open(src).read()
         for sym in re.findall(r'dlsym\(lib, "(\w+)"\)', text):
-            assert sym == "ds_experiments_attention_profile" or re.search(r"\b%s\(" % sym, hdr), f"{name}: {sym} is not in the header"
+            assert re.search(r"\b%s\(" % sym, hdr), f"{name}: {sym} is not in the header"
         subprocess.check_call([hipcc, "-O1", "-std=c++17", src, "-o", str(tmp_path / name), "-ldl"])
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Tile-level numpy model of the control flow of k_attention_fwd3 (csrc/ds_attention.hip, -DDS_EXPERIMENTS builds): the attention
-kernel generation that computes S of tile t + 1 beside the softmax of tile t inside one wave.  What it restates one to one:
+"""Tile-level numpy model of the control flow of generation 3 of the attention kernel (removed from csrc/ds_attention.hip, the kernel
+is in git history): the generation that computes S of tile t + 1 beside the softmax of tile t inside one wave.  What it restates one to one:
 the prologue, which K / V^T tile sits in which LDS buffer at which time (K runs one tile ahead of V^T), the two alternating S
 accumulator sets, the peeled last iteration with its key mask, the deferred running maximum, the order rescale -> P.V.  What it
 checks: every LDS read sees the tile the algorithm means (buffers start as NaN and carry a tag), no buffer is written in the

@@ -36,7 +36,6 @@ def main():
     dev = torch.device("cuda")
     if "attention" in which:
         from src import vit_mi355x as vm
-        tag = "v1" if os.environ.get("DS_ATT_V1") else ("v2 split" if os.environ.get("DS_ATT_SPLIT") else "v2")
         for name, n, bias, bb in (("beit-l 1025 +bias", 1025, True, B), ("dinov2-l 1370", 1370, False, B),
                                   ("dinov2-l 2443 (1080p)", 2443, False, 8), ("beit-l 4097 +bias (net 1024)", 4097, True, 8),
                                   ("vit-b 577", 577, False, B)):
@@ -55,7 +54,7 @@ def main():
             got = nat.attention_fwd(qk[:2], vt[:2], n, 0.125, bt)
             want = vm.attention_reference(qk[:2].float(), vt[:2].float(), n, 0.125, padded)
             err = (got.float()[:, :n] - want[:, :n]).abs().max().item()
-            print(f"attention [{tag}] {name} x{bb}: {ms:.3f} ms  {4.0 * n * n * hh * 64 * bb / ms / 1e9:.1f} TF/s  max|err| {err:.2e}")
+            print(f"attention [v2] {name} x{bb}: {ms:.3f} ms  {4.0 * n * n * hh * 64 * bb / ms / 1e9:.1f} TF/s  max|err| {err:.2e}")
     if "head" in which:
         conv3 = nn.Conv2d(128, 32, 3, padding=1).to(dev).half()
         conv1 = nn.Conv2d(32, 1, 1).to(dev).half()
