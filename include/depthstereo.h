@@ -225,6 +225,46 @@ int ds_colorize_u16(ds_ctx *ctx, const uint16_t *depth, int n, int h, int w, con
 /* convert_to_i16 alone (src/core.py:44-50): float32 or float64 input already in [0,1]. */
 int ds_convert_to_i16(ds_ctx *ctx, const void *arr, int is_f64, int64_t count, uint16_t *out, void *stream);
 
+/* pixel types of the custom-depth entry points: Pillow modes L (and a band of RGB / RGBX), I;16, I, F */
+#define DS_PIX_U8  0
+#define DS_PIX_U16 1
+#define DS_PIX_I32 2
+#define DS_PIX_F32 3
+
+/*
+ * ds_resize_lanczos -- Image.resize(size, Image.Resampling.LANCZOS) of the custom-depth ingest (src/core.py:147-153) as Pillow's
+ * Resample.c computes it: a horizontal pass when the width changes, then a vertical pass when the height changes, each rounded
+ * into the pixel type (8-bit: 22-bit fixed point from 2^21, clipped; 16-bit: float64 sum, round half away, below 0 -> 0, above
+ * 65535 -> 0xFF00 | low byte; int32: float64 sum, round half away; float32: float64 sum, one cast).  Taps in ascending order.
+ *   src        n images of in_h * in_w pixels of type `pix`; strides in ELEMENTS (a pixel stride of 3 or 4 reads band 0 of
+ *              interleaved RGB / RGBX in place)
+ *   dst        n * out_h * out_w pixels of the same type, dense
+ *   h_bounds   out_w * {first tap, tap count} int32;  h_coeffs  [h_taps][out_w] weights (TAP-MAJOR): float64, for DS_PIX_U8 the
+ *              int32 fixed-point weights.  v_* likewise for out_h.  Built on the host (the libm sin Pillow calls); the arrays of a
+ *              pass that does not run may be NULL.  A window that leaves the source or the table contributes nothing.
+ *   tmp        n * in_h * out_w pixels, needed when both passes run (the rounded intermediate)
+ * Equal sizes -> DS_EINVAL (nothing to resize); more than 1024 taps per output pixel -> DS_EUNSUPPORTED.  Asynchronous.
+ */
+int ds_resize_lanczos(ds_ctx *ctx, const void *src, int pix, int n, int in_h, int in_w, int64_t src_px_stride, int64_t src_row_stride,
+                      int64_t src_img_stride, void *dst, int out_h, int out_w, const int32_t *h_bounds, const void *h_coeffs, int h_taps,
+                      const int32_t *v_bounds, const void *v_coeffs, int v_taps, void *tmp, void *stream);
+
+/*
+ * ds_custom_depth_to_f64 -- the rest of the custom-depth ingest (src/core.py:155-174): np.asarray(dp, dtype="float") and the divide.
+ *   DS_CD_WIDEN        out = (double)pixel                                   (an ndarray depth map, :172)
+ *   DS_CD_SINGLE_BAND  out = pixel / 2^bits, bits = 8 if max < 256, 16 if max < 65536, else 32, max = the image's maximum
+ *                      as np.max takes it (a NaN wins, and then fails both tests)   (:156-165)
+ *   DS_CD_MULTI_BAND   out = pixel / 256 (the caller's pixel stride selects channel 0)   (:169-170)
+ *   src as above; out n*h*w doubles; workspace (SINGLE_BAND only) n * (2 + DS_CD_WORKSPACE_BLOCKS) doubles, of which the first
+ *   n * 2 hold {maximum, divisor} per image afterwards.  Asynchronous.
+ */
+#define DS_CD_WIDEN       0
+#define DS_CD_SINGLE_BAND 1
+#define DS_CD_MULTI_BAND  2
+#define DS_CD_WORKSPACE_BLOCKS 256
+int ds_custom_depth_to_f64(ds_ctx *ctx, const void *src, int pix, int n, int h, int w, int64_t src_px_stride, int64_t src_row_stride,
+                           int64_t src_img_stride, int rule, double *out, double *workspace, void *stream);
+
 /* element types of the tensor-core entry points */
 #define DS_DTYPE_F16  1
 #define DS_DTYPE_BF16 2

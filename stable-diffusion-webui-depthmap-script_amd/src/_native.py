@@ -25,7 +25,7 @@ EXPORTS = [
     "ds_convert_to_i16", "ds_profile_enable", "ds_profile_last_ms", "ds_stereo_last_stats", "ds_attention_fwd", "ds_attention_bias_pack", "ds_colorize_u16", "ds_residual_layernorm", "ds_boost_blend", "ds_upsample_bilinear_nhwc", "ds_dpt_head_tail", "ds_preprocess_bicubic", "ds_linear_reload_env", "ds_attention_reload_env", "ds_normalmap_selfcheck", "ds_normalmap_gradient_f16", "ds_normalmap_gradient_blur_f32",
     "ds_linear_shuffle", "ds_linear_readout", "ds_kernel_timer_enable", "ds_kernel_timer_read", "ds_kernel_timer_read_each", "ds_group_norm_nchw",
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
-    "ds_dwconv_nhwc",
+    "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64",
 ]
 
 
@@ -101,6 +101,8 @@ def lib():
             L.ds_bias_act_f32.argtypes = [vp, vp, vp, vp, vp, i64, ci, ci, vp]
             L.ds_relu_cat_f32.argtypes = [vp, vp, vp, vp, ci, i64, ci, ci, ci, vp]
             L.ds_dwconv_nhwc.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]
+            L.ds_resize_lanczos.argtypes = [vp, vp, ci, ci, ci, ci, i64, i64, i64, vp, ci, ci, vp, vp, ci, vp, vp, ci, vp, vp]
+            L.ds_custom_depth_to_f64.argtypes = [vp, vp, ci, ci, ci, ci, i64, i64, i64, ci, vp, vp, vp]
             L.ds_kernel_timer_enable.argtypes = [vp, ci]
             L.ds_kernel_timer_read.argtypes = [vp, ci, ctypes.POINTER(i64), ctypes.POINTER(cd)]
             L.ds_kernel_timer_read_each.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_float), i64, ctypes.POINTER(i64)]
@@ -303,6 +305,84 @@ def convert_to_i16(arr):
     _check(lib().ds_convert_to_i16(ctx_for(_dev_index(arr)), arr.data_ptr(), 1 if arr.dtype == torch.float64 else 0,
                                    arr.numel(), out.data_ptr(), _stream(arr)))
     return out
+
+
+# ---- custom-depth ingest (csrc/ds_resample.hip; host half: src/resample_model.py) -------------------------------------------------
+CD_WIDEN, CD_SINGLE_BAND, CD_MULTI_BAND = 0, 1, 2
+_CD_WORKSPACE_BLOCKS = 256                       # DS_CD_WORKSPACE_BLOCKS
+_coeff_cache = collections.OrderedDict()         # (device, fixed point?, in, out) -> (bounds, tap-major weights, taps) on the device
+
+
+def _pixel_plane(src):
+    """(DS_PIX_* id, n, h, w, pixel / row / image stride in elements) of a dense CUDA tensor [n,h,w] of uint8 / uint16 / int32 /
+    float32, or [n,h,w,c] uint8 (interleaved bands: band 0 is read in place)."""
+    torch = _torch()
+    from . import resample_model as rm
+    pix = {torch.uint8: rm.PIX_U8, torch.uint16: rm.PIX_U16, torch.int32: rm.PIX_I32, torch.float32: rm.PIX_F32}.get(src.dtype)
+    if pix is None or not src.is_cuda or not src.is_contiguous() or src.dim() not in (3, 4) or (src.dim() == 4 and pix != rm.PIX_U8):
+        raise DepthStereoError(f"unsupported pixel tensor: dtype {src.dtype}, shape {tuple(src.shape)}")
+    n, h, w = src.shape[:3]
+    c = src.shape[3] if src.dim() == 4 else 1
+    return pix, n, h, w, c, w * c, h * w * c
+
+
+def _lanczos_coeffs_on(device, fixed_point, in_size, out_size):
+    torch = _torch()
+    from . import resample_model as rm
+    key = (str(device), bool(fixed_point), int(in_size), int(out_size))
+    hit = _coeff_cache.get(key)
+    if hit is None:
+        taps, bounds, kk = rm.lanczos_coeffs(int(in_size), int(out_size))
+        if fixed_point:
+            kk = rm.fixed_point_coeffs(kk)
+        hit = (torch.from_numpy(np.array(bounds)).to(device), torch.from_numpy(np.array(kk.T, order='C')).to(device), taps)
+        _coeff_cache[key] = hit
+        while len(_coeff_cache) > 32:
+            _coeff_cache.popitem(last=False)
+    else:
+        _coeff_cache.move_to_end(key)
+    return hit
+
+
+def resize_lanczos(src, out_hw):
+    """Image.resize((out_w, out_h), Image.Resampling.LANCZOS) of a batch of planes, byte for byte as the installed Pillow computes it
+    (include/depthstereo.h: ds_resize_lanczos).  src: see _pixel_plane.  Returns [n, out_h, out_w] of src's dtype."""
+    torch = require_gpu()
+    from . import resample_model as rm
+    pix, n, in_h, in_w, px, row, img = _pixel_plane(src)
+    out_h, out_w = int(out_hw[0]), int(out_hw[1])
+    horiz, vert = out_w != in_w, out_h != in_h
+    dst = torch.empty((n, out_h, out_w), dtype=src.dtype, device=src.device)
+    hb = hk = vb = vk = tmp = None
+    ht = vt = 0
+    if horiz:
+        hb, hk, ht = _lanczos_coeffs_on(src.device, pix == rm.PIX_U8, in_w, out_w)
+    if vert:
+        vb, vk, vt = _lanczos_coeffs_on(src.device, pix == rm.PIX_U8, in_h, out_h)
+    if horiz and vert:
+        tmp = torch.empty((n, in_h, out_w), dtype=src.dtype, device=src.device)
+    CALLS["ds_resize_lanczos"] += 1
+    _check(lib().ds_resize_lanczos(ctx_for(_dev_index(src)), src.data_ptr(), pix, n, in_h, in_w, px, row, img, dst.data_ptr(), out_h, out_w,
+                                   hb.data_ptr() if horiz else None, hk.data_ptr() if horiz else None, ht,
+                                   vb.data_ptr() if vert else None, vk.data_ptr() if vert else None, vt,
+                                   tmp.data_ptr() if tmp is not None else None, _stream(src)))
+    return dst
+
+
+def custom_depth_to_f64(src, rule, out=None):
+    """np.asarray(depth, dtype="float") and the divide of the custom-depth ingest (include/depthstereo.h: ds_custom_depth_to_f64).
+    src: see _pixel_plane; rule: CD_WIDEN / CD_SINGLE_BAND (value / 2^bits by the image's maximum) / CD_MULTI_BAND (band 0 / 256).
+    Returns (float64 [n,h,w] -- `out` when given --, [n,2] float64 {maximum, divisor} per image for CD_SINGLE_BAND else None)."""
+    torch = require_gpu()
+    pix, n, h, w, px, row, img = _pixel_plane(src)
+    if out is None:
+        out = torch.empty((n, h, w), dtype=torch.float64, device=src.device)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (n, h, w) and out.is_contiguous() and out.device == src.device
+    ws = torch.empty((n * (2 + _CD_WORKSPACE_BLOCKS),), dtype=torch.float64, device=src.device) if rule == CD_SINGLE_BAND else None
+    CALLS["ds_custom_depth_to_f64"] += 1
+    _check(lib().ds_custom_depth_to_f64(ctx_for(_dev_index(src)), src.data_ptr(), pix, n, h, w, px, row, img, int(rule), out.data_ptr(),
+                                        ws.data_ptr() if ws is not None else None, _stream(src)))
+    return out, (ws[:2 * n].view(n, 2) if ws is not None else None)
 
 
 def colorize_u16(depth, vmin_vmax, lut_rgba):

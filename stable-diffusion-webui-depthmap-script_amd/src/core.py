@@ -79,7 +79,9 @@ class CoreGenerationFunnelInp:
 
 
 def _custom_depth_to_float(dp, image):
-    """Custom depthmap ingest (reference: src/core.py:145-174).  Host code: PIL resampling must be PIL's."""
+    """Custom depthmap ingest (reference: src/core.py:145-174) on the host: the route of every depth map the device ingest below does
+    not cover (RGBA / LA, whose alpha Pillow premultiplies for the resize; P, 1, I;16B; a mode LANCZOS refuses, for which the
+    reference falls back to the default filter; float64 and other arrays), and of all of them with CUSTOM_DEPTH_DEVICE off."""
     if isinstance(dp, Image.Image):
         if dp.width != image.width or dp.height != image.height:
             try:
@@ -108,6 +110,8 @@ def _custom_depth_to_float(dp, image):
 
 import ctypes as _ctypes
 import os as _os
+import types as _types
+import warnings as _warnings
 import threading as _threading
 import time as _time
 
@@ -115,6 +119,97 @@ import time as _time
 # through dpt_beit_large_512: one group of 32 -> 176 pairs/s, two pipelined groups of 16 -> 289 pairs/s (the PIL conversion
 # of a group overlaps the next group's device work)
 FUNNEL_BATCH_PIXELS = int(_os.environ.get("DS_FUNNEL_BATCH_PIXELS", 16 << 20))
+
+
+# ---- custom depth maps on the device --------------------------------------------------------------------------------------------
+# DS_CUSTOM_DEPTH_DEVICE=0 (or core.CUSTOM_DEPTH_DEVICE = False; read per call): every custom depth map takes _custom_depth_to_float.
+# On: a PIL depth map of mode L / I;16 / I / F / RGB and an ndarray of dtype uint8 / uint16 / int32 / float32 cross the link in their
+# own pixel type and size; Pillow's LANCZOS resize (restated in csrc/ds_resample.hip, coefficients from src/resample_model.py), the
+# widening to float64, the per-image maximum and the divide run on the compute stream.  Same float64 plane, bit for bit.
+CUSTOM_DEPTH_DEVICE = _os.environ.get("DS_CUSTOM_DEPTH_DEVICE", "1") != "0"
+_DEVICE_DEPTH_MODES = ("L", "I;16", "I", "F", "RGB")
+_DEVICE_DEPTH_DTYPES = (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.int32), np.dtype(np.float32))
+_probe_said = [False]
+
+
+def _pillow_resampler_verified():
+    """The kernel restates the arithmetic of the Pillow it was written against, not a documented contract: once per process a numpy
+    model of it is compared with the installed Pillow (resample_model.pillow_matches_model, like _arrow_layout_verified below); on any
+    difference PIL depth maps keep the host route for the rest of the process, and the funnel says so once."""
+    from . import resample_model
+    ok = resample_model.pillow_matches_model()
+    if not ok and not _probe_said[0]:
+        _probe_said[0] = True
+        _warnings.warn("depthmap: this Pillow's LANCZOS resize differs from the arithmetic of ds_resize_lanczos; "
+                       "custom depth maps are ingested on the host (as with DS_CUSTOM_DEPTH_DEVICE=0)")
+    return ok
+
+
+def _depth_device_key(dp, size):
+    """What decides the route of one custom depth map for an image of `size` (width, height): None = the host route, else the key
+    under which consecutive depth maps share a launch -- ("pil", mode, its size) or ("array", dtype)."""
+    from . import resample_model
+    if isinstance(dp, Image.Image):
+        if dp.mode not in _DEVICE_DEPTH_MODES or dp.width < 1 or dp.height < 1 or not _pillow_resampler_verified():
+            return None
+        for n_in, n_out in ((dp.width, size[0]), (dp.height, size[1])):
+            if n_in != n_out and int(np.ceil(3.0 * max(n_in / n_out, 1.0))) * 2 + 1 > resample_model.MAX_TAPS:
+                return None                                  # ds_resize_lanczos: DS_EUNSUPPORTED
+        return ("pil", dp.mode, dp.size)
+    if isinstance(dp, np.ndarray) and dp.dtype in _DEVICE_DEPTH_DTYPES and dp.shape == (size[1], size[0]):
+        return ("array", dp.dtype)
+    return None                                              # float64 and everything np.asarray has to interpret; a size mismatch asserts there
+
+
+def _ingest_custom_depth(depthmaps, size, device, upload, stats=None):
+    """reference: src/core.py:145-174 for a batch of depth maps that belong to images of one `size` (width, height) -> float64 cuda
+    tensor [B, H, W].  Consecutive depth maps of one (mode, size) form one launch; the others go one by one, each by its own route.
+    upload(list of equal-shape arrays, tag, torch dtype) -> device tensor [len, ...]."""
+    torch = _native._torch()
+    w, h = size
+    use_device = CUSTOM_DEPTH_DEVICE
+    keys = [_depth_device_key(dp, size) if use_device else None for dp in depthmaps]
+    like = _types.SimpleNamespace(width=w, height=h)
+    if all(k is None for k in keys):                         # (also the whole of the switched-off route: one upload of float64 planes)
+        outs = [_custom_depth_to_float(dp, like) for dp in depthmaps]
+        if stats is not None:
+            stats["custom_depth_host"] = stats.get("custom_depth_host", 0) + len(depthmaps)
+        return upload([np.asarray(o, dtype=np.float64) for o in outs], "cdepth", torch.float64)
+    out_t = torch.empty((len(depthmaps), h, w), dtype=torch.float64, device=device)
+    at, run = 0, 0
+    while at < len(depthmaps):
+        end = at + 1
+        while keys[at] is not None and end < len(depthmaps) and keys[end] == keys[at]:
+            end += 1
+        part, key, tag = depthmaps[at:end], keys[at], "cdepth%d" % run
+        if key is None:
+            o = np.asarray(_custom_depth_to_float(part[0], like), dtype=np.float64)
+            out_t[at:end].copy_(upload([o], tag, torch.float64))
+        else:
+            arrays = [np.asarray(dp) for dp in part] if len(part) == 1 else list(_host_pool().map(np.asarray, part))
+            px = upload(arrays, tag, getattr(torch, arrays[0].dtype.name))
+            if key[0] == "array":
+                rule = _native.CD_WIDEN
+            else:
+                rule = _native.CD_MULTI_BAND if key[1] == "RGB" else _native.CD_SINGLE_BAND
+                if key[2] != (w, h):                                                             # :147-153
+                    px = _native.resize_lanczos(px, (h, w))
+            _native.custom_depth_to_f64(px, rule, out=out_t[at:end])                              # :155-172
+        if stats is not None:
+            name = "custom_depth_host" if key is None else "custom_depth_device"
+            stats[name] = stats.get(name, 0) + (end - at)
+        at, run = end, run + 1
+    return out_t
+
+
+def ingest_custom_depth_batch(depthmaps, size):
+    """Custom depth maps (PIL images or arrays, as `inputdepthmaps` of the funnel takes them) for images of `size` = (width, height)
+    -> what the reference's ingest (src/core.py:145-174) makes of each, as a float64 cuda tensor [B, H, W] that stays on the device:
+    the input of _native.convert_to_i16, and from there of create_stereoimages_batch / create_normalmap_batch."""
+    torch = _native.require_gpu()
+    device = torch.device('cuda', torch.cuda.current_device())
+    return _ingest_custom_depth(list(depthmaps), (int(size[0]), int(size[1])), device,
+                                lambda arrays, tag, dtype: torch.from_numpy(np.stack(arrays)).to(device))
 
 
 # ---- PIL -> pinned staging without the interpreter lock ----------------------------------------------------------------------
@@ -385,7 +480,7 @@ def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=Non
         return t
 
     def upload(arrays, tag, dtype):
-        st = _staging.get(gen, tag, (b,) + arrays[0].shape, dtype)
+        st = _staging.get(gen, tag, (len(arrays),) + arrays[0].shape, dtype)
         stn = st.numpy()
         for j, a in enumerate(arrays):
             np.copyto(stn[j], a)
@@ -426,8 +521,7 @@ def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=Non
         img_t = upload_pixels("img", lambda im: np.asarray(im, dtype=np.uint8), rgb=images[0].mode == "RGB")
     mesh_source = None
     if custom:
-        outs = [_custom_depth_to_float(inputdepthmaps[i], inputimages[i]) for i in idxs]         # :145-174 (host: PIL)
-        out_t = upload([np.asarray(o, dtype=np.float64) for o in outs], "cdepth", torch.float64)
+        out_t = _ingest_custom_depth([inputdepthmaps[i] for i in idxs], (w, h), device, upload, stats)   # :145-174
         d16 = _native.convert_to_i16(out_t)                                                      # :211
         mesh_source = out_t
     else:
@@ -578,7 +672,8 @@ _copy_streams = {}
 # own and publishes it here when its generator finishes, so interleaved generators cannot mix their numbers.  FUNNEL_STATS is the call
 # that ENDED last ('call' = its serial number, 'finished' = whether its generator ran to completion); a call that starts does not
 # touch it, so a generator that interleaves with another one cannot wipe the other's published numbers; the last few calls stay
-# readable by serial number in FUNNEL_STATS_BY_CALL.
+# readable by serial number in FUNNEL_STATS_BY_CALL.  'custom_depth_device' / 'custom_depth_host': how many custom depth maps of the
+# call were ingested by the kernels / by _custom_depth_to_float.
 FUNNEL_STATS = {}
 FUNNEL_STATS_BY_CALL = {}
 _funnel_calls = [0]
@@ -790,7 +885,7 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
     pil_blocks_held = _tune_pil_allocator()
     with _funnel_calls_lock:
         _funnel_calls[0] += 1
-        stats = {"finished": False, "call": _funnel_calls[0]}
+        stats = {"finished": False, "call": _funnel_calls[0], "custom_depth_device": 0, "custom_depth_host": 0}
     _t_start = _time.perf_counter()
     pending = launched = None
     if _TRACE:
