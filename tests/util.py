@@ -56,3 +56,62 @@ def smooth_depth(H, W, seed):
     x0, y0 = int(rng.uniform(0, W / 2)), int(rng.uniform(0, H / 2))
     f[y0:y0 + H // 4, x0:x0 + W // 3] += 1.0
     return f.astype(np.float32)
+
+
+# ---- exact-integer operands and per-element rounding bounds for the half-precision GEMM / convolution tests ------------------------
+MANTISSA_BITS = {"float16": 10, "bfloat16": 7}
+MIN_NORMAL_EXP = {"float16": -14, "bfloat16": -126}
+
+
+def ternary(g, shape, density):
+    """float64 tensor of {-1, 0, +1}: nonzero with probability `density`, both signs equally likely (generator g, CPU)."""
+    import torch
+    keep = torch.rand(shape, generator=g) < density
+    sign = torch.randint(0, 2, shape, generator=g) * 2 - 1
+    return torch.where(keep, sign, torch.zeros_like(sign)).double()
+
+
+def small_ints(g, shape, bound):
+    """float64 tensor of integers drawn uniformly from [-bound, bound]."""
+    import torch
+    return torch.randint(-bound, bound + 1, shape, generator=g).double()
+
+
+def ulp_spacing(ref64, dtype):
+    """Spacing of `dtype` (float16 / bfloat16) at the float64 values rounded to it: 2^(floor(log2 |r|) - mantissa bits), and the
+    subnormal spacing below the smallest normal number (the construction of test_gpu_midas_small._f16_within_bound, for both types)."""
+    import torch
+    name = str(dtype).replace("torch.", "")
+    r = ref64.to(dtype).double().abs()
+    _, e = torch.frexp(r.clamp(min=2.0 ** MIN_NORMAL_EXP[name]))          # |r| = m 2^e with m in [1/2, 1)
+    return torch.ldexp(torch.ones_like(r), e - 1 - MANTISSA_BITS[name])
+
+
+def ulp_distance(got, ref64, floor=0.0):
+    """Distance between every element of got and the float64 value rounded to got's type, in units in the last place of that
+    type at the rounded value -- a whole number.  floor > 0: the unit is never finer than `floor` (bfloat16 keeps float32's
+    exponent range, so near zero its ulp says nothing about an fp32 computation; float16's ends at its subnormal spacing 2^-24)."""
+    g = got.detach().cpu()
+    r = ref64.to(g.dtype).double()
+    return (g.double() - r).abs() / ulp_spacing(ref64, g.dtype).clamp(min=floor)
+
+
+def rounding_bound_ratio(got, ref64, abs_terms, k_total):
+    """Single-rounding bound of a half-precision GEMM with fp32 accumulation and an fp32 epilogue, per element:
+        |got - ref64| <= 1/2 ulp_out(ref64) + 2 (k_total + 4) 2^-24 abs_terms,
+    abs_terms = sum_k |x_k w_k| + |bias| + ... the same formula on the absolute values.  One fp32 rounding per accumulation step
+    and epilogue operation, a FULL ulp (2^-24 relative, not half) each since the MFMA's internal rounding of its partial sums is
+    not documented as round-to-nearest.  Returns (worst error / bound, outputs more than one ulp from ref64 rounded)."""
+    g = got.detach().cpu()
+    err = (g.double() - ref64).abs()
+    bound = 0.5 * ulp_spacing(ref64, g.dtype) + 2.0 * (k_total + 4) * 2.0 ** -24 * abs_terms
+    return float((err / bound).max()), int((ulp_distance(g, ref64) > 1).sum())
+
+
+def first_mismatches(got, want, limit=5):
+    """"<count> of <total> differ: (index, got, want) ..." for two tensors of one shape (a readable failure of torch.equal)."""
+    import torch
+    g, w = got.detach().cpu().double(), want.detach().cpu().double()
+    bad = torch.nonzero(g != w)
+    rows = ["(%s: got %g, want %g)" % (", ".join(str(int(i)) for i in ix), g[tuple(ix)], w[tuple(ix)]) for ix in bad[:limit]]
+    return "%d of %d differ: %s" % (bad.shape[0], g.numel(), " ".join(rows))
