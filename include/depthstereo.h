@@ -491,6 +491,20 @@ int ds_conv3x3_nhwc(ds_ctx *ctx, const void *x, const void *w, const void *bias,
                     int batch, int height, int width, int in_channels, int out_channels, int act, int dtype, void *stream);
 
 /*
+ * ds_conv3x3_nhwc_circular -- ds_conv3x3_nhwc on the CIRCULARLY padded image:
+ *     y = act(conv3x3(x circularly padded by 1 in H and W, W) + bias [+ res1] [+ res2])
+ * i.e. nn.Conv2d(padding_mode='circular'), which the reference's TILING_MODE sets on every module whose type is exactly
+ * nn.Conv2d (src/depthmap_generation.py:251-260) so that the depth map of a tileable texture tiles.  Same parameter list, shape
+ * rules, epilogues (act 0, 2 and 6) and dtype rules as ds_conv3x3_nhwc.  The kernel is the same implicit GEMM with one more
+ * compile-time mode: where the zero-padding form fetches a neighbour outside the image from the zero line, this one fetches the
+ * pixel on the opposite side (row -1 = row height - 1, row height = row 0, likewise the columns; height == 1 or width == 1 wraps
+ * a pixel onto itself, as F.pad(mode='circular') does).  Tap order, channel order and the fp32 chain per output element are the
+ * zero-padding kernel's: every pixel at least one step from the border gets bit-identical output from the two entry points.
+ */
+int ds_conv3x3_nhwc_circular(ds_ctx *ctx, const void *x, const void *w, const void *bias, const void *res1, const void *res2, void *y,
+                             int batch, int height, int width, int in_channels, int out_channels, int act, int dtype, void *stream);
+
+/*
  * ds_upsample_bilinear_nhwc -- torch.nn.functional.interpolate(x, size, mode="bilinear", align_corners) for channels_last
  * activations: the x2 upsamples of the DPT decoders (dmidas/blocks.py:429-431; ddepth_anything_v2/.../util/blocks.py:141-145;
  * the heads' Interpolate, dmidas/dpt_depth.py:151, dpt.py:146).  in [batch, in_h, in_w, channels], out [batch, out_h, out_w,
@@ -512,6 +526,18 @@ int ds_upsample_bilinear_nhwc(ds_ctx *ctx, const void *in, void *out, int batch,
 int ds_dpt_head_tail(ds_ctx *ctx, const void *x, int batch, int in_h, int in_w, int out_h, int out_w,
                      const void *conv3_wfrag, const float *conv3_bias, const float *conv1_weight, float conv1_bias,
                      int relu_out, void *out, int dtype, void *stream);
+
+/*
+ * ds_dpt_head_tail_circular -- ds_dpt_head_tail for a head whose 3x3 convolution has padding_mode='circular' (the reference's
+ * TILING_MODE, src/depthmap_generation.py:251-260, applied to dmidas/dpt_depth.py:150-158 and ddepth_anything_v2/.../dpt.py:105-111).
+ * Same parameter list.  The bilinear upsample is unchanged -- it is not a convolution; the 3x3 128->32 convolution reads the
+ * UPSAMPLED map circularly: the halo row -1 is upsampled row out_h - 1, row out_h is row 0, likewise the columns.
+ * This entry point ALWAYS launches the tile kernel (k_dpt_head_tail), whatever DS_HEAD_MODE / DS_HEAD_PERSIST say: the
+ * persistent and the streaming kernel pad with zeros only.
+ */
+int ds_dpt_head_tail_circular(ds_ctx *ctx, const void *x, int batch, int in_h, int in_w, int out_h, int out_w,
+                              const void *conv3_wfrag, const float *conv3_bias, const float *conv1_weight, float conv1_bias,
+                              int relu_out, void *out, int dtype, void *stream);
 
 /*
  * ds_gconv3x3_nhwc_f32 -- the grouped 3x3 convolution of the ResNeXt-101 32x8d bottlenecks of LeReS, Boost's base estimator, in

@@ -378,7 +378,11 @@ struct HeadTailParams {
     float sy, sx;
 };
 
-template <int BF16, int RPW>      // RPW = output rows per wave; tile = 4*RPW rows x 32 columns
+// CIRC = 1 (ds_dpt_head_tail_circular): the 3x3 convolution pads the UPSAMPLED map circularly (padding_mode='circular', what the
+// reference's TILING_MODE sets on every Conv2d, src/depthmap_generation.py:251-260): the halo position oy = -1 is upsampled row
+// oh - 1, oy = oh is row 0, likewise in x, wrapped BEFORE the source coordinates are derived -- the upsample itself is not a
+// convolution and stays as it is.  Nothing is "outside" then.
+template <int BF16, int RPW, int CIRC = 0>      // RPW = output rows per wave; tile = 4*RPW rows x 32 columns
 __global__ __launch_bounds__(256) void k_dpt_head_tail(HeadTailParams P)
 {
     typedef typename eo_traits<BF16>::T T;
@@ -400,8 +404,17 @@ __global__ __launch_bounds__(256) void k_dpt_head_tail(HeadTailParams P)
             live[u] = i < HT_NPIX * 16;
             const int pix = min(i, HT_NPIX * 16 - 1) >> 4, chunk = i & 15;
             const int r = pix / HT_PW, c = pix - r * HT_PW;
-            const int oy = ty0 - 1 + r, ox = tx0 - 1 + c;
-            inside[u] = live[u] && oy >= 0 && oy < P.oh && ox >= 0 && ox < P.ow;
+            int oy = ty0 - 1 + r, ox = tx0 - 1 + c;
+            if constexpr (CIRC) {
+                // rows / columns -1 and oh / ow wrap; a tile that sticks out of the image by more than the halo holds pixels past
+                // that, which feed no stored output: they are clamped into the image like the zero-padding form's source coordinates
+                oy = oy < 0 ? oy + P.oh : (oy >= P.oh ? oy - P.oh : oy);
+                ox = ox < 0 ? ox + P.ow : (ox >= P.ow ? ox - P.ow : ox);
+                oy = min(oy, P.oh - 1); ox = min(ox, P.ow - 1);
+                inside[u] = live[u];
+            } else {
+                inside[u] = live[u] && oy >= 0 && oy < P.oh && ox >= 0 && ox < P.ow;
+            }
             const float fy = P.sy * max(oy, 0), fx = P.sx * max(ox, 0);
             const int y0 = min((int)fy, P.ih - 1), x0 = min((int)fx, P.iw - 1);
             const int y1 = min(y0 + 1, P.ih - 1), x1 = min(x0 + 1, P.iw - 1);
@@ -891,14 +904,16 @@ __global__ __launch_bounds__(512) void k_dpt_head_tail_s(HeadTailParams P, int s
     }
 }
 
-DS_API int ds_dpt_head_tail(ds_ctx *ctx, const void *x, int batch, int in_h, int in_w, int out_h, int out_w,
-                            const void *conv3_wfrag, const float *conv3_bias, const float *conv1_weight, float conv1_bias,
-                            int relu_out, void *out, int dtype, void *stream)
+// circular = 1: ds_dpt_head_tail_circular -- always the tile kernel (the persistent and the streaming kernel pad with zeros only)
+static int ht_head_tail(const int circular, ds_ctx *ctx, const void *x, int batch, int in_h, int in_w, int out_h, int out_w,
+                        const void *conv3_wfrag, const float *conv3_bias, const float *conv1_weight, float conv1_bias,
+                        int relu_out, void *out, int dtype, void *stream)
 {
-    DS_REQUIRE(ctx && x && conv3_wfrag && conv3_bias && conv1_weight && out, DS_EINVAL, "ds_dpt_head_tail: null argument");
-    DS_REQUIRE(batch > 0 && batch <= 65535 && in_h > 0 && in_w > 0 && out_h > 0 && out_w > 0, DS_EINVAL, "ds_dpt_head_tail: bad shape");
-    DS_REQUIRE(dtype == DS_DTYPE_F16 || dtype == DS_DTYPE_BF16, DS_EINVAL, "ds_dpt_head_tail: dtype must be f16 or bf16");
-    DS_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)conv3_wfrag & 15) == 0, DS_EINVAL, "ds_dpt_head_tail: 16-byte alignment");
+    const char *NAME = circular ? "ds_dpt_head_tail_circular" : "ds_dpt_head_tail";          // goes into the messages
+    DS_REQUIRE(ctx && x && conv3_wfrag && conv3_bias && conv1_weight && out, DS_EINVAL, "%s: null argument", NAME);
+    DS_REQUIRE(batch > 0 && batch <= 65535 && in_h > 0 && in_w > 0 && out_h > 0 && out_w > 0, DS_EINVAL, "%s: bad shape", NAME);
+    DS_REQUIRE(dtype == DS_DTYPE_F16 || dtype == DS_DTYPE_BF16, DS_EINVAL, "%s: dtype must be f16 or bf16", NAME);
+    DS_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)conv3_wfrag & 15) == 0, DS_EINVAL, "%s: 16-byte alignment", NAME);
     DS_HIP_CHECK(hipSetDevice(ctx->device));
     HeadTailParams P;
     P.x = x; P.wfrag = conv3_wfrag; P.b2 = conv3_bias; P.w3 = conv1_weight; P.b3 = conv1_bias; P.out = out;
@@ -911,6 +926,7 @@ DS_API int ds_dpt_head_tail(ds_ctx *ctx, const void *x, int batch, int in_h, int
     int mode = 2;
     { const char *e = getenv("DS_HEAD_PERSIST"); if (e && atoi(e) == 0) mode = 0; }
     { const char *e = getenv("DS_HEAD_MODE"); if (e) mode = !strcmp(e, "stream") ? 2 : (!strcmp(e, "tile") ? 0 : (!strcmp(e, "persist") ? 1 : mode)); }
+    if (circular) mode = 0;
     if (mode == 2 && !(3.f * P.sy < 1.99f && 8.f * P.sx < 4.99f)) mode = 1;      // the staging tile of the streaming kernel: 4 x 7 source pixels
     if (mode == 2) {
         int ncu = 0, dev = 0;
@@ -923,7 +939,7 @@ DS_API int ds_dpt_head_tail(ds_ctx *ctx, const void *x, int batch, int in_h, int
         { const char *e = getenv("DS_HEAD_SEG"); if (e && atoi(e) >= 4) seg_rows = (atoi(e) + 3) & ~3; }
         const int nseg = (out_h + seg_rows - 1) / seg_rows;
         const long long nitems = (long long)strips_x * nseg * batch;
-        DS_REQUIRE(nitems < (1ll << 30), DS_EUNSUPPORTED, "ds_dpt_head_tail: too many work items");
+        DS_REQUIRE(nitems < (1ll << 30), DS_EUNSUPPORTED, "%s: too many work items", NAME);
         int dbg = 0;                                        // timing ablations (WRONG results): -DDS_EXPERIMENTS builds only
 #ifdef DS_EXPERIMENTS
         { const char *e = getenv("DS_HEAD_ABLATE"); if (e) dbg = atoi(e); }        // 1: no steady-state producer work, 2: no MFMAs
@@ -944,7 +960,7 @@ DS_API int ds_dpt_head_tail(ds_ctx *ctx, const void *x, int batch, int in_h, int
     if (mode == 1) {
         const int tiles_x = (out_w + HT_TW - 1) / HT_TW, tiles_y = (out_h + HTP_TH - 1) / HTP_TH;
         const long long nt = (long long)tiles_x * tiles_y * batch;
-        DS_REQUIRE(nt < (1ll << 30), DS_EUNSUPPORTED, "ds_dpt_head_tail: too many tiles");
+        DS_REQUIRE(nt < (1ll << 30), DS_EUNSUPPORTED, "%s: too many tiles", NAME);
         int ncu = 0, dev = 0;
         DS_HIP_CHECK(hipGetDevice(&dev));
         DS_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
@@ -967,17 +983,38 @@ DS_API int ds_dpt_head_tail(ds_ctx *ctx, const void *x, int batch, int in_h, int
     const int th = 4 * s_rpw;
     const size_t lds = (size_t)(th + 2) * HT_PW * 256;
     dim3 grid((out_w + HT_TW - 1) / HT_TW, (out_h + th - 1) / th, batch);
-    DS_REQUIRE(grid.y <= 65535, DS_EUNSUPPORTED, "ds_dpt_head_tail: image too tall");
-#define HT_LAUNCH(BF, RP) do {                                                                                              \
-        DS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dpt_head_tail<BF, RP>),                           \
+    DS_REQUIRE(grid.y <= 65535, DS_EUNSUPPORTED, "%s: image too tall", NAME);
+#define HT_LAUNCH(BF, RP, CI) do {                                                                                          \
+        DS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dpt_head_tail<BF, RP, CI>),                       \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                            \
-        hipLaunchKernelGGL((k_dpt_head_tail<BF, RP>), grid, dim3(256), lds, (hipStream_t)stream, P);                        \
+        hipLaunchKernelGGL((k_dpt_head_tail<BF, RP, CI>), grid, dim3(256), lds, (hipStream_t)stream, P);                    \
     } while (0)
-    if (dtype == DS_DTYPE_F16) { if (s_rpw == 2) HT_LAUNCH(0, 2); else HT_LAUNCH(0, 1); }
-    else { if (s_rpw == 2) HT_LAUNCH(1, 2); else HT_LAUNCH(1, 1); }
+    if (circular) {
+        if (dtype == DS_DTYPE_F16) { if (s_rpw == 2) HT_LAUNCH(0, 2, 1); else HT_LAUNCH(0, 1, 1); }
+        else { if (s_rpw == 2) HT_LAUNCH(1, 2, 1); else HT_LAUNCH(1, 1, 1); }
+    } else {
+        if (dtype == DS_DTYPE_F16) { if (s_rpw == 2) HT_LAUNCH(0, 2, 0); else HT_LAUNCH(0, 1, 0); }
+        else { if (s_rpw == 2) HT_LAUNCH(1, 2, 0); else HT_LAUNCH(1, 1, 0); }
+    }
 #undef HT_LAUNCH
     DS_HIP_CHECK(hipGetLastError());
     return DS_OK;
+}
+
+DS_API int ds_dpt_head_tail(ds_ctx *ctx, const void *x, int batch, int in_h, int in_w, int out_h, int out_w,
+                            const void *conv3_wfrag, const float *conv3_bias, const float *conv1_weight, float conv1_bias,
+                            int relu_out, void *out, int dtype, void *stream)
+{
+    return ht_head_tail(0, ctx, x, batch, in_h, in_w, out_h, out_w, conv3_wfrag, conv3_bias, conv1_weight, conv1_bias, relu_out, out, dtype, stream);
+}
+
+// The head tail with the 3x3 convolution padded circularly (TILING_MODE; k_dpt_head_tail<.., CIRC = 1>).  ALWAYS the tile kernel,
+// whatever DS_HEAD_MODE / DS_HEAD_PERSIST say: the persistent and the streaming kernel exist for zero padding only.
+DS_API int ds_dpt_head_tail_circular(ds_ctx *ctx, const void *x, int batch, int in_h, int in_w, int out_h, int out_w,
+                                     const void *conv3_wfrag, const float *conv3_bias, const float *conv1_weight, float conv1_bias,
+                                     int relu_out, void *out, int dtype, void *stream)
+{
+    return ht_head_tail(1, ctx, x, batch, in_h, in_w, out_h, out_w, conv3_wfrag, conv3_bias, conv1_weight, conv1_bias, relu_out, out, dtype, stream);
 }
 
 

@@ -102,7 +102,7 @@ template <> struct ln_traits<1> {
 struct LinParams {
     const void *x, *w, *bias;
     const void *res1, *res2;    // optional addends of the epilogue, laid out like y
-    const void *zeros;          // CONV: >= 128 zero bytes (the padding ring of the image)
+    const void *zeros;          // CONV 1 / 2: >= 128 zero bytes (the padding ring of the image)
     void *y;
     int M, N, K;                // K = reduction length (CONV: 9 * C)
     int nbm, nbn;
@@ -256,7 +256,11 @@ template <int N> __device__ __forceinline__ void ln_wait_vm() { asm volatile("s_
 // (read x, write h) shrinks to a statistics pass (read x).  RES: number of residual addends (res1, res2).  CONV: 0 = x is a dense [M, K] matrix; 1 = x is an NHWC image [batch, H, W, C] and the
 // GEMM is the implicit one of a 3 x 3, stride 1, zero-padded convolution: row m = output pixel, K-tile kt = 64 channels
 // kt / 9 of tap kt % 9 (tap-fastest: the pixels of a chunk are fetched once and hit in L2 for the other eight taps), whose
-// source is the same 128 bytes of the pixel shifted by (dy, dx) -- or the zero line.
+// source is the same 128 bytes of the pixel shifted by (dy, dx) -- or the zero line.  CONV 2 = CONV 1 with ReLU on x.
+// CONV 3 / 4 = CONV 1 / 2 with CIRCULAR padding (padding_mode='circular' of nn.Conv2d, what TILING_MODE sets on every convolution:
+// reference src/depthmap_generation.py:251-260): a neighbour outside the image is the pixel on the opposite side, so nothing comes
+// from the zero line -- the DMA source of a missing row moves by -+ H W pixels, of a missing column by -+ W pixels (LN_STAGE).  Same
+// K-tile order, same MFMAs, same epilogue: the fp32 chain of an output element is the zero-padding kernel's, term for term.
 // NH = 1: a tile is 256 rows x 128 columns (the head's 256 -> 128 convolution of the DPT decoders, dmidas/dpt_depth.py:150): the
 // wave grid stays 2 x 4, every wave column owns 32 columns = the B0 half alone.  The phase schedule, the LDS map and every
 // counted wait stay exactly as they are -- the B1 half-tile is still staged (with B0's source: a dummy that keeps the DMA
@@ -333,17 +337,23 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
         unsigned koff_ = (unsigned)(kt) * 128u;                                                                          \
         const unsigned dst_ = ((kind) >> 1) * LN_B_BASE + ((kind) & 1) * 2 * LN_HALF + (s) * LN_HALF + lds_stage;  /* LDS address */ \
         int dy_ = 0, dx_ = 0, aoff_ = (int)koff_;                                                                        \
+        long wrapy_ = 0, wrapx_ = 0;     /* CONV 3 / 4: what brings a neighbour outside the image back in on the other side */ \
         if (CONV) {              /* K-tile kt = tap kt % 9 of channel chunk kt / 9: the nine taps of one 64-channel chunk */ \
             const int cc_ = ((kt) * 7282) >> 16, tap_ = (kt) - 9 * cc_;      /* follow each other, their pixels stay in L2 */ \
             dy_ = ((tap_ * 11) >> 5) - 1; dx_ = tap_ - 3 * (dy_ + 1) - 1;                                                \
             aoff_ = cc_ * 128 + (dy_ * P.W + dx_) * rowbytes;                                                            \
             koff_ = (unsigned)(tap_ * P.cpt + cc_) * 128u;               /* the weights stay [out][tap][in] */             \
+            if (CONV >= 3) { wrapy_ = -(long)dy_ * ((long)P.H * P.W * rowbytes); wrapx_ = -(long)dx_ * ((long)P.W * rowbytes); } \
         }                                                                                                                \
         /* uniform 64-bit base of this K-tile (scalar arithmetic) + the thread's loop-invariant 32-bit offset */           \
         const unsigned char *ub_ = ((kind) < 2) ? xb + ((long)aoff_ + (long)(((kind) & 1) * a_half))                     \
                                                 : wb + (size_t)(((kind) & 1) * b_half + koff_);                          \
         _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                               \
-            if (CONV && (kind) < 2) {                                                                                    \
+            if (CONV >= 3 && (kind) < 2) {   /* row y + dy outside: row (y + dy) -+ H; column x + dx outside: column (x + dx) -+ W. */ \
+                const unsigned sh_ = 6 * (2 * ((kind) & 1) + i_);    /* H == 1 / W == 1: the pixel itself, as F.pad(mode='circular') */ \
+                const long wrap_ = (((okA >> (sh_ + dy_ + 1)) & 1u) ? 0l : wrapy_) + (((okA >> (sh_ + 4 + dx_)) & 1u) ? 0l : wrapx_); \
+                ln_dma_v(ub_ + ((long)srcA[i_] + wrap_), dst_ + i_ * 1024);                                              \
+            } else if (CONV && (kind) < 2) {                                                                             \
                 const unsigned sh_ = 6 * (2 * ((kind) & 1) + i_);                                                        \
                 const unsigned ok_ = (okA >> (sh_ + dy_ + 1)) & (okA >> (sh_ + 4 + dx_)) & 1u;                           \
                 const unsigned char *g_ = ok_ ? ub_ + (size_t)srcA[i_] : (const unsigned char *)P.zeros;                 \
@@ -409,12 +419,12 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
                 fa[h][rb_][ks_] = *(const V8 *)(lds + offA[ks_] + ((h) * 2 * LN_HALF + (s) * LN_HALF + rb_ * 4096));     \
         }                                                                                                                \
     } while (0)
-    // CONV 2: ReLU on the x operand (the `conv1(relu(x))` of a residual unit, dmidas/blocks.py:361-363): applied to the fragments
+    // CONV 2 / 4: ReLU on the x operand (the `conv1(relu(x))` of a residual unit, dmidas/blocks.py:361-363): applied to the fragments
     // in the MEMORY part of the phase that read them -- 32 packed maxima per wave, issued as the reads return, beside the other
     // wave-row's MFMAs -- instead of a pass over the activation in front of the launch (the convolutions run the 32x32x16 form)
 #define LN_RELU_A(h)                                                                                                     \
     do {                                                                                                                 \
-        if constexpr (CONV == 2) {                                                                                       \
+        if constexpr (CONV == 2 || CONV == 4) {                                                                          \
             _Pragma("unroll") for (int rb_ = 0; rb_ < 2; ++rb_) _Pragma("unroll") for (int ks_ = 0; ks_ < 4; ++ks_)      \
                 fa[h][rb_][ks_] = TR::relu(fa[h][rb_][ks_]);                                                             \
         }                                                                                                                \
@@ -605,6 +615,10 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
     const int hi8 = 8 * (lane >> 5);
     LN_ZERO_NULL_BIAS();
     T *yb = (T *)P.y;
+    // (CONV 3 / 4: the base stays a scalar HERE, so that the per-lane store address is formed per tile instead of being hoisted out
+    // of the tile loop and spilled -- the circular gather has no register to spare, and a reload in the epilogue would be a
+    // vmcnt(0) behind the next tile's prologue DMAs)
+    if constexpr (CONV >= 3) asm volatile("" : "+s"(yb));
     const T *r1 = (const T *)P.res1, *r2 = (const T *)P.res2;
     if (early && next < nwg) {
         // the bias vectors have been in flight since before the last iteration: waiting for them HERE (the empty
@@ -1462,27 +1476,29 @@ static int ln_dispatch_dense(ds_ctx *ctx, const LinParams &P, int act, hipStream
     return ln_launch<BF16, 0, 0, 0>(ctx, P, st);
 }
 
-template <int BF16>
+// CIRC: 0 = zero padding (CONV 1, with ReLU on x CONV 2), 1 = circular padding (CONV 3 / 4)
+template <int BF16, int CIRC>
 static int ln_dispatch_conv(ds_ctx *ctx, const LinParams &P, int act, hipStream_t st)
 {
+    constexpr int CV = CIRC ? 3 : 1, CVR = CIRC ? 4 : 2;
     const int res = P.res1 ? (P.res2 ? 2 : 1) : 0;
-    if (act & 4) {                           // ReLU on x (CONV 2): the first convolution of a residual unit -- ReLU out, no addends
-        if (P.N % 256 == 0 && (act & 3) == 2 && res == 0) return ln_launch<BF16, 2, 2, 0>(ctx, P, st);
-        ds_set_error("ds_conv3x3_nhwc: act 4 (ReLU on x) is built for act 2 | 4 without residual operands and out_channels %% 256 == 0");
+    if (act & 4) {                           // ReLU on x (CONV 2 / 4): the first convolution of a residual unit -- ReLU out, no addends
+        if (P.N % 256 == 0 && (act & 3) == 2 && res == 0) return ln_launch<BF16, 2, CVR, 0>(ctx, P, st);
+        ds_set_error("ds_conv3x3_nhwc[_circular]: act 4 (ReLU on x) is built for act 2 | 4 without residual operands and out_channels %% 256 == 0");
         return DS_EUNSUPPORTED;
     }
     if (P.N % 256 != 0) {                    // 128-column tiles (NH = 1): the head convolution, no residual operands
-        if (act == 2) return ln_launch<BF16, 2, 1, 0, 0, 1>(ctx, P, st);
-        return ln_launch<BF16, 0, 1, 0, 0, 1>(ctx, P, st);
+        if (act == 2) return ln_launch<BF16, 2, CV, 0, 0, 1>(ctx, P, st);
+        return ln_launch<BF16, 0, CV, 0, 0, 1>(ctx, P, st);
     }
     if (act == 2) {
-        if (res == 2) return ln_launch<BF16, 2, 1, 2>(ctx, P, st);
-        if (res == 1) return ln_launch<BF16, 2, 1, 1>(ctx, P, st);
-        return ln_launch<BF16, 2, 1, 0>(ctx, P, st);
+        if (res == 2) return ln_launch<BF16, 2, CV, 2>(ctx, P, st);
+        if (res == 1) return ln_launch<BF16, 2, CV, 1>(ctx, P, st);
+        return ln_launch<BF16, 2, CV, 0>(ctx, P, st);
     }
-    if (res == 2) return ln_launch<BF16, 0, 1, 2>(ctx, P, st);
-    if (res == 1) return ln_launch<BF16, 0, 1, 1>(ctx, P, st);
-    return ln_launch<BF16, 0, 1, 0>(ctx, P, st);
+    if (res == 2) return ln_launch<BF16, 0, CV, 2>(ctx, P, st);
+    if (res == 1) return ln_launch<BF16, 0, CV, 1>(ctx, P, st);
+    return ln_launch<BF16, 0, CV, 0>(ctx, P, st);
 }
 
 DS_API int ds_linear(ds_ctx *ctx, const void *x, const void *w, const void *bias, void *y, int64_t rows, int64_t out_features,
@@ -1538,23 +1554,25 @@ DS_API int ds_linear_residual(ds_ctx *ctx, const void *x, const void *w, const v
     return gamma ? ln_launch<1, 3, 0, 1>(ctx, P, st) : ln_launch<1, 0, 0, 1>(ctx, P, st);
 }
 
-DS_API int ds_conv3x3_nhwc(ds_ctx *ctx, const void *x, const void *w, const void *bias, const void *res1, const void *res2, void *y,
-                           int batch, int height, int width, int in_channels, int out_channels, int act, int dtype, void *stream)
+// the two entry points share everything but the padding: NAME goes into the messages, CIRC picks the instantiations
+template <int CIRC>
+static int ln_conv3x3(const char *NAME, ds_ctx *ctx, const void *x, const void *w, const void *bias, const void *res1, const void *res2, void *y,
+                      int batch, int height, int width, int in_channels, int out_channels, int act, int dtype, void *stream)
 {
-    DS_REQUIRE(ctx && x && w && y, DS_EINVAL, "ds_conv3x3_nhwc: null argument");
-    DS_REQUIRE(batch > 0 && height > 0 && width > 0 && height < 32768 && width < 32768, DS_EINVAL, "ds_conv3x3_nhwc: bad image shape");
+    DS_REQUIRE(ctx && x && w && y, DS_EINVAL, "%s: null argument", NAME);
+    DS_REQUIRE(batch > 0 && height > 0 && width > 0 && height < 32768 && width < 32768, DS_EINVAL, "%s: bad image shape", NAME);
     DS_REQUIRE((int64_t)batch * height * width < (1ll << 31) - 256 && (int64_t)batch * height * width >= 256, DS_EINVAL,
-               "ds_conv3x3_nhwc: batch * height * width must be in [256, 2^31)");
+               "%s: batch * height * width must be in [256, 2^31)", NAME);
     DS_REQUIRE(in_channels >= 64 && in_channels % 64 == 0 && (9 * in_channels / 64) % 2 == 0 && in_channels <= 4096, DS_EINVAL,
-               "ds_conv3x3_nhwc: in_channels must be a multiple of 128 (<= 4096)");
-    DS_REQUIRE(out_channels > 0 && out_channels % 128 == 0, DS_EINVAL, "ds_conv3x3_nhwc: out_channels must be a multiple of 128");
+               "%s: in_channels must be a multiple of 128 (<= 4096)", NAME);
+    DS_REQUIRE(out_channels > 0 && out_channels % 128 == 0, DS_EINVAL, "%s: out_channels must be a multiple of 128", NAME);
     DS_REQUIRE(out_channels % 256 == 0 || (!res1 && !res2), DS_EUNSUPPORTED,
-               "ds_conv3x3_nhwc: residual operands need out_channels to be a multiple of 256 (the 128-column tiles have no residual epilogue)");
-    DS_REQUIRE(act == 0 || act == 2 || act == 6, DS_EINVAL, "ds_conv3x3_nhwc: act must be 0 (none), 2 (ReLU) or 6 (ReLU, and ReLU on x)");
-    DS_REQUIRE(dtype == DS_DTYPE_F16 || dtype == DS_DTYPE_BF16, DS_EINVAL, "ds_conv3x3_nhwc: dtype must be f16 or bf16");
+               "%s: residual operands need out_channels to be a multiple of 256 (the 128-column tiles have no residual epilogue)", NAME);
+    DS_REQUIRE(act == 0 || act == 2 || act == 6, DS_EINVAL, "%s: act must be 0 (none), 2 (ReLU) or 6 (ReLU, and ReLU on x)", NAME);
+    DS_REQUIRE(dtype == DS_DTYPE_F16 || dtype == DS_DTYPE_BF16, DS_EINVAL, "%s: dtype must be f16 or bf16", NAME);
     DS_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)y & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0) &&
                ((uintptr_t)res1 & 15) == 0 && ((uintptr_t)res2 & 15) == 0,
-               DS_EINVAL, "ds_conv3x3_nhwc: x, w, y, bias, res1 and res2 must be 16-byte aligned");
+               DS_EINVAL, "%s: x, w, y, bias, res1 and res2 must be 16-byte aligned", NAME);
     int rc = ds_ctx_reserve(ctx, &ctx->zero_line, &ctx->zero_line_bytes, 256);
     if (rc != DS_OK) return rc;
     if (!ctx->zero_line_cleared) {          // once per context; waited for, so that a second stream of the same context never
@@ -1570,14 +1588,28 @@ DS_API int ds_conv3x3_nhwc(ds_ctx *ctx, const void *x, const void *w, const void
     P.nbm = (P.M + 255) / 256; P.nbn = out_channels % 256 == 0 ? out_channels / 256 : out_channels / 128;
     P.H = height; P.W = width; P.C = in_channels; P.cpt = in_channels / 64; P.magic = 65536 / P.cpt + 1;
     for (int kt = 0; kt < P.K / 64; ++kt)
-        DS_REQUIRE(((kt * 7282) >> 16) == kt / 9, DS_EUNSUPPORTED, "ds_conv3x3_nhwc: K-tile arithmetic does not cover %d channels", in_channels);
+        DS_REQUIRE(((kt * 7282) >> 16) == kt / 9, DS_EUNSUPPORTED, "%s: K-tile arithmetic does not cover %d channels", NAME, in_channels);
     P.ldy = out_channels;
     P.kt_kind = DS_KT_CONV3X3;
 #ifdef DS_EXPERIMENTS
     P.ablate = getenv("DS_LIN_ABLATE") ? atoi(getenv("DS_LIN_ABLATE")) : 0;
     P.stagger = getenv("DS_LIN_STAGGER_US") ? (int)(atof(getenv("DS_LIN_STAGGER_US")) * 100.0) : 0;
 #endif
-    return dtype == DS_DTYPE_F16 ? ln_dispatch_conv<0>(ctx, P, act, (hipStream_t)stream) : ln_dispatch_conv<1>(ctx, P, act, (hipStream_t)stream);
+    return dtype == DS_DTYPE_F16 ? ln_dispatch_conv<0, CIRC>(ctx, P, act, (hipStream_t)stream) : ln_dispatch_conv<1, CIRC>(ctx, P, act, (hipStream_t)stream);
+}
+
+DS_API int ds_conv3x3_nhwc(ds_ctx *ctx, const void *x, const void *w, const void *bias, const void *res1, const void *res2, void *y,
+                           int batch, int height, int width, int in_channels, int out_channels, int act, int dtype, void *stream)
+{
+    return ln_conv3x3<0>("ds_conv3x3_nhwc", ctx, x, w, bias, res1, res2, y, batch, height, width, in_channels, out_channels, act, dtype, stream);
+}
+
+// The same convolution on the circularly padded image (nn.Conv2d(padding_mode='circular'), which the reference's TILING_MODE sets on
+// every Conv2d: src/depthmap_generation.py:251-260): k_linear256<.., CONV 3 / 4>, see the template's comment.
+DS_API int ds_conv3x3_nhwc_circular(ds_ctx *ctx, const void *x, const void *w, const void *bias, const void *res1, const void *res2, void *y,
+                                    int batch, int height, int width, int in_channels, int out_channels, int act, int dtype, void *stream)
+{
+    return ln_conv3x3<1>("ds_conv3x3_nhwc_circular", ctx, x, w, bias, res1, res2, y, batch, height, width, in_channels, out_channels, act, dtype, stream);
 }
 
 // V^T of an encoder block straight out of the GEMM: vt[b][c][n] = sum_k w_v[c][k] h[b][n][k] (the reference computes

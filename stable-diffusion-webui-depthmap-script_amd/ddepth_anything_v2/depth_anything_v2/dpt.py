@@ -88,8 +88,10 @@ class DPTHead(nn.Module):
         path_1 = s.refinenet1(path_2, l1)
         out = vm.conv2d(s.output_conv1, path_1)                # 256 -> 128: the in-tree implicit GEMM (256 x 128 tiles) where it fills the chip
         size = (int(patch_h * 14), int(patch_w * 14))
-        if vm.half_on_gpu(out) and tuple(s.output_conv2[0].weight.shape) == (32, 128, 3, 3):
-            # upsample -> conv3x3 128->32 -> ReLU -> conv1x1 -> ReLU in one MFMA kernel (ds_dpt_head_tail)
+        if (vm.half_on_gpu(out) and tuple(s.output_conv2[0].weight.shape) == (32, 128, 3, 3)
+                and s.output_conv2[0].padding_mode in ('zeros', 'circular') and vm.circular_hip_ok(s.output_conv2[0])):
+            # upsample -> conv3x3 128->32 -> ReLU -> conv1x1 -> ReLU in one MFMA kernel (ds_dpt_head_tail; TILING_MODE makes the
+            # convolution circular: ds_dpt_head_tail_circular; DS_CONV_CIRCULAR=0: the torch sequence below, which honours padding_mode)
             from src import _native
             return _native.dpt_head_tail(out, size, s.output_conv2[0], s.output_conv2[2], relu_out=True)
         out = vm.interpolate_bilinear(out, size=size, align_corners=True)

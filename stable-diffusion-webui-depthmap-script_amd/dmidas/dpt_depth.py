@@ -106,7 +106,8 @@ class DPT(nn.Module):
             return y
         if (vm.half_on_gpu(path_1) and isinstance(head[1], Interpolate)
                 and head[1].mode == "bilinear" and head[1].align_corners and tuple(head[2].weight.shape) == (32, 128, 3, 3)
-                and head[2].padding_mode == 'zeros'):          # TILING_MODE makes the convolutions circular: library path
+                and head[2].padding_mode in ('zeros', 'circular') and vm.circular_hip_ok(head[2])):
+            # (TILING_MODE makes the convolutions circular: ds_dpt_head_tail_circular; DS_CONV_CIRCULAR=0: the torch sequence below)
             # upsample x2 -> conv3x3 128->32 -> ReLU -> conv1x1 -> ReLU in one MFMA kernel (ds_dpt_head_tail)
             from src import _native
             # the head's first convolution (256 -> 128): the in-tree implicit GEMM on 256 x 128 tiles where the launch fills the chip

@@ -25,7 +25,7 @@ EXPORTS = [
     "ds_convert_to_i16", "ds_profile_enable", "ds_profile_last_ms", "ds_stereo_last_stats", "ds_attention_fwd", "ds_attention_bias_pack", "ds_colorize_u16", "ds_residual_layernorm", "ds_boost_blend", "ds_upsample_bilinear_nhwc", "ds_dpt_head_tail", "ds_preprocess_bicubic", "ds_linear_reload_env", "ds_attention_reload_env", "ds_normalmap_selfcheck", "ds_normalmap_gradient_f16", "ds_normalmap_gradient_blur_f32",
     "ds_linear_shuffle", "ds_linear_readout", "ds_kernel_timer_enable", "ds_kernel_timer_read", "ds_kernel_timer_read_each", "ds_group_norm_nchw",
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
-    "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64",
+    "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
 ]
 
 
@@ -82,6 +82,7 @@ def lib():
             L.ds_boost_blend.argtypes = [vp, vp, i64, ci, ci, vp, ci, vp, ci, vp, ci, vp]
             L.ds_upsample_bilinear_nhwc.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
             L.ds_dpt_head_tail.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, ctypes.c_float, ci, vp, ci, vp]
+            L.ds_dpt_head_tail_circular.argtypes = L.ds_dpt_head_tail.argtypes
             L.ds_preprocess_bicubic.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_float),
                                                 ctypes.POINTER(ctypes.c_float), ci, vp]
             L.ds_reassemble_readout.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]
@@ -91,6 +92,7 @@ def lib():
             L.ds_linear_residual.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, ci, vp]
             L.ds_linear_vt.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, ci, vp]
             L.ds_conv3x3_nhwc.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
+            L.ds_conv3x3_nhwc_circular.argtypes = L.ds_conv3x3_nhwc.argtypes
             L.ds_linear_shuffle.argtypes = [vp, vp, vp, vp, vp, i64, i64, ci, ci, ci, ci, vp]
             L.ds_linear_readout.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, vp]
             L.ds_row_stats.argtypes = [vp, vp, vp, i64, ci, ctypes.c_float, ci, vp]
@@ -874,12 +876,24 @@ def conv3x3_supported(conv, x):
             and x.shape[0] * x.shape[2] * x.shape[3] >= 256)
 
 
+def conv3x3_circular_supported(conv, x):
+    """What ds_conv3x3_nhwc_circular takes: conv3x3_supported's conditions with padding_mode == 'circular' (TILING_MODE,
+    src/depthmap_generation.py: apply_tiling_mode)."""
+    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1)
+            and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding_mode == 'circular'
+            and conv.in_channels % 128 == 0 and conv.out_channels % 128 == 0 and x.dim() == 4 and x.shape[1] == conv.in_channels
+            and x.shape[0] * x.shape[2] * x.shape[3] >= 256)
+
+
 def conv3x3(conv, x, relu=False, res1=None, res2=None, relu_in=False):
     """[relu](conv(x) + bias [+ res1] [+ res2]) for a 3x3 nn.Conv2d on a float16 / bfloat16 CUDA activation, channels_last
-    in and out (include/depthstereo.h: ds_conv3x3_nhwc).  The [out, 3, 3, in] weight image is cached on the module.
+    in and out (include/depthstereo.h: ds_conv3x3_nhwc; padding_mode == 'circular': ds_conv3x3_nhwc_circular).  The [out, 3, 3, in]
+    weight image is cached on the module (one image for both entry points).
     relu_in: conv(relu(x)) with the maximum taken inside the kernel (needs relu, no residual operands, out % 256 == 0)."""
     torch = require_gpu()
-    assert x.is_cuda and x.dtype in (torch.float16, torch.bfloat16) and conv3x3_supported(conv, x)
+    circular = conv.padding_mode == 'circular'
+    assert x.is_cuda and x.dtype in (torch.float16, torch.bfloat16)
+    assert conv3x3_circular_supported(conv, x) if circular else conv3x3_supported(conv, x)
     x = x.contiguous(memory_format=torch.channels_last)
     b, c, h, w = x.shape
     key = (conv.weight.data_ptr(), conv.weight._version, x.dtype, None if conv.bias is None else conv.bias._version)
@@ -895,11 +909,12 @@ def conv3x3(conv, x, relu=False, res1=None, res2=None, relu_in=False):
     out = torch.empty((b, conv.out_channels, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     for r in (res1, res2):
         assert r is None or (r.shape == out.shape and r.dtype == x.dtype and r.is_contiguous(memory_format=torch.channels_last))
-    CALLS["ds_conv3x3_nhwc"] += 1
-    _check(lib().ds_conv3x3_nhwc(ctx_for(_dev_index(x)), x.data_ptr(), wk.data_ptr(), None if bk is None else bk.data_ptr(),
-                                 None if res1 is None else res1.data_ptr(), None if res2 is None else res2.data_ptr(),
-                                 out.data_ptr(), b, h, w, c, conv.out_channels, (2 if relu else 0) | (4 if relu_in else 0),
-                                 1 if x.dtype == torch.float16 else 2, _stream(x)))
+    name = "ds_conv3x3_nhwc_circular" if circular else "ds_conv3x3_nhwc"
+    CALLS[name] += 1
+    _check(getattr(lib(), name)(ctx_for(_dev_index(x)), x.data_ptr(), wk.data_ptr(), None if bk is None else bk.data_ptr(),
+                                None if res1 is None else res1.data_ptr(), None if res2 is None else res2.data_ptr(),
+                                out.data_ptr(), b, h, w, c, conv.out_channels, (2 if relu else 0) | (4 if relu_in else 0),
+                                1 if x.dtype == torch.float16 else 2, _stream(x)))
     return out
 
 
@@ -1003,7 +1018,8 @@ def upsample_bilinear(x, size=None, scale_factor=None, align_corners=True):
 
 def dpt_head_tail(x, size, conv3, conv1, relu_out=True):
     """upsample(x, size, bilinear, align_corners=True) -> conv3 (3x3, 128->32) -> ReLU -> conv1 (1x1, 32->1) -> ReLU, fused
-    (include/depthstereo.h: ds_dpt_head_tail).  x: NCHW-shaped [B,128,h,w] float16/bfloat16 CUDA tensor (any memory format;
+    (include/depthstereo.h: ds_dpt_head_tail; conv3.padding_mode == 'circular': ds_dpt_head_tail_circular, the 3x3 convolution
+    reading the upsampled map circularly).  x: NCHW-shaped [B,128,h,w] float16/bfloat16 CUDA tensor (any memory format;
     channels_last is zero-copy).  conv3 / conv1: the nn.Conv2d modules.  Returns [B, 1, H, W]."""
     torch = require_gpu()
     b, c, ih, iw = x.shape
@@ -1026,8 +1042,10 @@ def dpt_head_tail(x, size, conv3, conv1, relu_out=True):
     _, wf, b2, w3, b3 = hit
     oh, ow = int(size[0]), int(size[1])
     out = torch.empty((b, 1, oh, ow), dtype=x.dtype, device=x.device)
-    CALLS["ds_dpt_head_tail"] += 1
-    _check(lib().ds_dpt_head_tail(ctx_for(_dev_index(x)), xin.data_ptr(), b, ih, iw, oh, ow, wf.data_ptr(), b2.data_ptr(),
-                                  w3.data_ptr(), b3, 1 if relu_out else 0, out.data_ptr(),
-                                  1 if x.dtype == torch.float16 else 2, _stream(x)))
+    assert conv3.padding_mode in ('zeros', 'circular') and tuple(conv3.padding) == (1, 1)
+    name = "ds_dpt_head_tail_circular" if conv3.padding_mode == 'circular' else "ds_dpt_head_tail"
+    CALLS[name] += 1
+    _check(getattr(lib(), name)(ctx_for(_dev_index(x)), xin.data_ptr(), b, ih, iw, oh, ow, wf.data_ptr(), b2.data_ptr(),
+                                w3.data_ptr(), b3, 1 if relu_out else 0, out.data_ptr(),
+                                1 if x.dtype == torch.float16 else 2, _stream(x)))
     return out

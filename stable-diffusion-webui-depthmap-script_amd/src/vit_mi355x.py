@@ -510,6 +510,15 @@ CONV_HIP = os.environ.get("DS_CONV", "1") != "0"
 CONV_HIP_MIN_TILES = int(os.environ.get("DS_CONV_MIN_TILES", 48))
 CONV_HEAD_HIP = os.environ.get("DS_CONV_HEAD", "1") != "0"      # A/B switch: the 256 x 128 tiles (out_channels % 256 == 128)
 CONV_RELU_IN = os.environ.get("DS_CONV_RELU_IN", "1") != "0"    # A/B switch: conv1(relu(x)) of a residual unit with the ReLU inside the kernel
+# Product switch: 0 = convolutions with padding_mode == 'circular' (TILING_MODE, src/depthmap_generation.py: apply_tiling_mode) go
+# to the library -- the 3x3s through MIOpen and separate bias / ReLU passes, the heads through the unfused torch sequence -- instead
+# of ds_conv3x3_nhwc_circular / ds_dpt_head_tail_circular and the circularly padded gather of the strided 3x3
+CONV_CIRCULAR_HIP = os.environ.get("DS_CONV_CIRCULAR", "1") != "0"
+
+
+def circular_hip_ok(conv):
+    """False for a circular convolution under DS_CONV_CIRCULAR=0; True for everything else."""
+    return CONV_CIRCULAR_HIP or getattr(conv, "padding_mode", "zeros") != "circular"
 
 
 def conv3x3_hip_ok(conv, x):
@@ -519,11 +528,12 @@ def conv3x3_hip_ok(conv, x):
     if conv.out_channels % 256 != 0 and not CONV_HEAD_HIP:
         return False
     tiles = (x.shape[0] * x.shape[2] * x.shape[3] + 255) // 256 * ((conv.out_channels + 255) // 256)
-    return _native.conv3x3_supported(conv, x) and tiles >= (1 if invariant() else CONV_HIP_MIN_TILES)
+    supported = _native.conv3x3_supported(conv, x) or (CONV_CIRCULAR_HIP and _native.conv3x3_circular_supported(conv, x))
+    return supported and tiles >= (1 if invariant() else CONV_HIP_MIN_TILES)
 
 
 def conv2d(conv, x):
-    """conv(x): ds_conv3x3_nhwc where it applies (scratch.layerN_rn of the decoders), the library otherwise."""
+    """conv(x): ds_conv3x3_nhwc[_circular] where it applies (scratch.layerN_rn of the decoders), the library otherwise."""
     if conv3x3_hip_ok(conv, x):
         from . import _native
         return _native.conv3x3(conv, x)
@@ -622,17 +632,20 @@ def strided3x3_hip_ok(layer, x):
     if not (invariant() and LINEAR_HIP == "all" and half_on_gpu(x) and x.dim() == 4 and type(layer) is nn.Conv2d):
         return False
     return (tuple(layer.kernel_size) == (3, 3) and tuple(layer.stride) == (2, 2) and tuple(layer.padding) == (1, 1) and layer.groups == 1
-            and tuple(layer.dilation) == (1, 1) and layer.padding_mode == "zeros" and layer.out_channels % 256 == 0
+            and tuple(layer.dilation) == (1, 1) and layer.out_channels % 256 == 0
+            and (layer.padding_mode == "zeros" or (layer.padding_mode == "circular" and CONV_CIRCULAR_HIP))
             and layer.in_channels % 128 == 0 and 9 * layer.in_channels <= 16384 and x.shape[1] == layer.in_channels)
 
 
 def conv_strided3x3(layer, x):
-    """layer(x) for a 3x3 / stride 2 / padding 1 convolution as gather + GEMM: the 3 x 3 windows of the zero padded NHWC map are
-    gathered once ([B, ho, wo, 3, 3, C], a strided view copied to rows), then ds_linear with the bias in its epilogue."""
+    """layer(x) for a 3x3 / stride 2 / padding 1 convolution as gather + GEMM: the 3 x 3 windows of the zero padded (TILING_MODE:
+    circularly padded) NHWC map are gathered once ([B, ho, wo, 3, 3, C], a strided view copied to rows), then ds_linear with the
+    bias in its epilogue."""
     from . import _native
     b, c, h, w = x.shape
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-    xp = F.pad(x, (1, 1, 1, 1)).permute(0, 2, 3, 1).contiguous()          # [B, h + 2, w + 2, C]
+    xp = F.pad(x, (1, 1, 1, 1), mode="circular") if layer.padding_mode == "circular" else F.pad(x, (1, 1, 1, 1))
+    xp = xp.permute(0, 2, 3, 1).contiguous()                              # [B, h + 2, w + 2, C]
     sb, sh, sw, sc = xp.stride()
     rows = xp.as_strided((b, ho, wo, 3, 3, c), (sb, 2 * sh, 2 * sw, sh, sw, sc)).reshape(b * ho * wo, 9 * c)
     y = _native.linear(rows, _gemm_weight(layer, x, 9 * c), layer.bias)
