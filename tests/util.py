@@ -108,6 +108,46 @@ def rounding_bound_ratio(got, ref64, abs_terms, k_total):
     return float((err / bound).max()), int((ulp_distance(g, ref64) > 1).sum())
 
 
+def bilinear_taps(n_in, n_out, align_corners=True):
+    """One axis of the bilinear upsample as include/depthstereo.h defines it (ds_upsample_bilinear_nhwc, ds_dpt_head_tail), in
+    float32 like the kernels and torch: s = (n_in - 1) / (n_out - 1) as a float32 quotient (0 when n_out == 1), f = s * o -- or
+    s = n_in / n_out, f = max(s * (o + 0.5) - 0.5, 0) without align_corners --, i0 = min(int(f), n_in - 1), i1 = min(i0 + 1,
+    n_in - 1), t = f - i0.  Returns (i0, i1, t): int64, int64 and float32 arrays of n_out entries."""
+    f32 = np.float32
+    o = np.arange(n_out, dtype=np.float32)
+    if align_corners:
+        s = f32(n_in - 1) / f32(n_out - 1) if n_out > 1 else f32(0.0)
+        f = s * o
+    else:
+        s = f32(n_in) / f32(n_out)
+        f = np.maximum(s * (o + f32(0.5)) - f32(0.5), f32(0.0))
+    assert f.dtype == np.float32
+    i0 = np.minimum(f.astype(np.int64), n_in - 1)
+    i1 = np.minimum(i0 + 1, n_in - 1)
+    return i0, i1, f - i0.astype(np.float32)
+
+
+def bilinear_ref(x, size, align_corners=True, taps_x=None):
+    """Bilinear resize of a float64 NHWC tensor x [B, H, W, C] to size (oh, ow): the four weights (1 - ty) (1 - tx), (1 - ty) tx,
+    ty (1 - tx), ty tx are float32 products of bilinear_taps (part of the definition), everything after that is float64 and nothing
+    is rounded.  taps_x replaces bilinear_taps along x (a test that corrupts its own reference).  Returns (u, sum |weight * value|)."""
+    import torch
+    oh, ow = size
+    y0, y1, ty = bilinear_taps(x.shape[1], oh, align_corners)
+    x0, x1, tx = taps_x if taps_x is not None else bilinear_taps(x.shape[2], ow, align_corners)
+    one = np.float32(1.0)
+    wy, wx = ((one - ty)[:, None], ty[:, None]), ((one - tx)[None, :], tx[None, :])
+    u, s = 0.0, 0.0
+    for iy, a in ((y0, wy[0]), (y1, wy[1])):
+        for ix, b in ((x0, wx[0]), (x1, wx[1])):
+            w = a * b
+            assert w.dtype == np.float32
+            w64 = torch.from_numpy(w.astype(np.float64))[None, :, :, None]
+            v = x[:, torch.from_numpy(iy)[:, None], torch.from_numpy(ix)[None, :]]          # [B, oh, ow, C]
+            u, s = u + w64 * v, s + w64 * v.abs()
+    return u, s
+
+
 def first_mismatches(got, want, limit=5):
     """"<count> of <total> differ: (index, got, want) ..." for two tensors of one shape (a readable failure of torch.equal)."""
     import torch
