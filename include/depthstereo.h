@@ -190,6 +190,34 @@ int ds_normalmap_gradient_blur_f32(ds_ctx *ctx, const float *depth, int n, int h
                                    uint8_t *out, void *stream);
 
 /*
+ * ds_normalmap_wrap, ds_normalmap_f64_wrap, ds_normalmap_gradient_f32_wrap, ds_normalmap_gradient_f16_wrap,
+ * ds_normalmap_gradient_blur_f32_wrap -- the five entry points above on a depth map that is ONE PERIOD OF A TILING: the normal map
+ * of a tileable depth map tiles.  The reference has no such mode and says so (src/normalmap_generation.py:16, "TODO: Tiling can be
+ * improved (gradients could be matched)"): its borders put a frame around the normal map of a seamless texture.  Same parameter
+ * lists, shape rules, dtype rules, error codes and kernel timer (DS_KT_NORMALMAP) as the entry point of the same name without
+ * `_wrap`; the kernels are the same ones with one more compile-time mode that changes only which sample a tap outside the image
+ * reads:
+ *   cv2.Sobel / cv2.GaussianBlur taps (BORDER_REFLECT_101 above: index -1 reads 1, index size reads size - 2): here index i reads
+ *     i mod size, a true modulo -- -1 reads size - 1, size reads 0, and a kernel wider than the image goes round more than once;
+ *   np.gradient (above: f[1] - f[0] at index 0, f[size - 1] - f[size - 2] at index size - 1, (f[i + 1] - f[i - 1]) / 2 between):
+ *     here (f[(i + 1) mod size] - f[(i - 1) mod size]) / 2 at every index, the two ends included.
+ * Tap order, operation order and every rounding are those of the entry point without `_wrap`.  Hence, with
+ *   R = pre_blur / 2 + (max(sobel_ksize, 3) / 2 for Sobel, 1 for np.gradient) + post_blur / 2     (integer divisions, 0 for a blur
+ *   that is off),
+ *   wrap(d) = plain(np.pad(d, R, mode='wrap'))[R:R+h, R:R+w]     bit for bit,
+ * the result commutes with np.roll bit for bit, and every pixel at least R from the border gets the same bytes from both entry
+ * points.  Images of a batch stay independent: the neighbour across a border is a sample of the same image.
+ */
+int ds_normalmap_wrap(ds_ctx *ctx, const uint16_t *depth, int n, int h, int w, int pre_blur,
+                      int sobel_ksize, int post_blur, int invert, uint8_t *out, void *stream);
+int ds_normalmap_f64_wrap(ds_ctx *ctx, const double *depth, int n, int h, int w, int pre_blur,
+                          int sobel_ksize, int post_blur, int invert, uint8_t *out, void *stream);
+int ds_normalmap_gradient_f32_wrap(ds_ctx *ctx, const float *depth, int n, int h, int w, int invert, uint8_t *out, void *stream);
+int ds_normalmap_gradient_f16_wrap(ds_ctx *ctx, const void *depth, int n, int h, int w, int invert, uint8_t *out, void *stream);
+int ds_normalmap_gradient_blur_f32_wrap(ds_ctx *ctx, const float *depth, int n, int h, int w, int pre_blur, int post_blur, int invert,
+                                        uint8_t *out, void *stream);
+
+/*
  * ds_normalmap_selfcheck -- device self-test of the fused normal-map kernels' arithmetic (tests): their square root and reciprocal
  * are the generic float64 expansions WITHOUT range scaling and special-case fix-ups (dead for n^2 = zx^2 + zy^2 + 1 in [1, 2^22],
  * src/normalmap_generation.py:34-39); the kernel compares them with sqrt() and 1.0 / n on n^2 = K / 2^18, K = k0 + stride * i,

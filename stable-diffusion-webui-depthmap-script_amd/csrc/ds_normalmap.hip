@@ -19,6 +19,22 @@ __device__ __forceinline__ int nm_reflect101(int i, int n)
     return i;
 }
 
+// ---- border mode (compile-time WRAP of every kernel that looks across the border) ---------------------------------------------------
+// WRAP 0: the reference's borders -- BORDER_REFLECT_101 for cv2.Sobel / cv2.GaussianBlur, one-sided differences at the two ends for
+//         np.gradient.  These instantiations are the kernels as they were before the parameter existed, instruction for instruction.
+// WRAP 1: the image is one period of a tiling: every tap index is taken modulo the image size (a true modulo: a 63-tap kernel on a
+//         5-pixel row is legal), and np.gradient is the halved central difference at every pixel, the two ends included.  Same tap
+//         order, operation order and roundings: the result is normalmap(np.pad(d, R, mode='wrap'))[R:R+h, R:R+w] bit for bit (R = the
+//         summed radii of the passes), and it commutes with np.roll.  (The reference leaves this open: src/normalmap_generation.py:16,
+//         "TODO: Tiling can be improved (gradients could be matched)".)
+__device__ __forceinline__ int nm_mod(int i, int n)                  // i mod n in [0, n) for any i
+{
+    i %= n;
+    return i < 0 ? i + n : i;
+}
+__device__ __forceinline__ int nm_wrap_prev(int i, int n) { return i > 0 ? i - 1 : n - 1; }      // (i - 1) mod n for i in [0, n)
+__device__ __forceinline__ int nm_wrap_next(int i, int n) { return i + 1 < n ? i + 1 : 0; }      // (i + 1) mod n for i in [0, n)
+
 // normal = (zx, -zy, 1)/|.| ; (+1)/2*256 clipped to [0, 255.9] ; truncate   (:34-39, :51-54)
 // The kernels are bound by float64 VALU issue, not by memory (round 3: ~160 vector instructions per pixel), so the arithmetic is
 // kept to what the result needs:
@@ -48,7 +64,7 @@ __device__ __forceinline__ void nm_store(double zx, double zy, uint8_t *o)
 #define NM_BX 64
 #define NM_BY 4
 
-template <int SOBEL3>
+template <int SOBEL3, int WRAP>
 __global__ __launch_bounds__(NM_BX * NM_BY) void k_normalmap_fused(const uint16_t *__restrict__ depth, int h, int w, int invert,
                                                                    uint8_t *__restrict__ out)
 {
@@ -61,13 +77,16 @@ __global__ __launch_bounds__(NM_BX * NM_BY) void k_normalmap_fused(const uint16_
 #define NMV(yy, xx) (((double)d[(size_t)(yy) * w + (xx)] * sgn) / 256.0)        /* :20-21 */
     double zx, zy;
     if (SOBEL3) {
-        const int xm = nm_reflect101(x - 1, w), xp = nm_reflect101(x + 1, w);
-        const int ym = nm_reflect101(y - 1, h), yp = nm_reflect101(y + 1, h);
+        const int xm = WRAP ? nm_wrap_prev(x, w) : nm_reflect101(x - 1, w), xp = WRAP ? nm_wrap_next(x, w) : nm_reflect101(x + 1, w);
+        const int ym = WRAP ? nm_wrap_prev(y, h) : nm_reflect101(y - 1, h), yp = WRAP ? nm_wrap_next(y, h) : nm_reflect101(y + 1, h);
         const double p00 = NMV(ym, xm), p01 = NMV(ym, x), p02 = NMV(ym, xp);
         const double p10 = NMV(y, xm), p12 = NMV(y, xp);
         const double p20 = NMV(yp, xm), p21 = NMV(yp, x), p22 = NMV(yp, xp);
         zx = (p02 - p00) + 2.0 * (p12 - p10) + (p22 - p20);                     /* cv2.Sobel dx, ksize 3 */
         zy = (p20 - p00) + 2.0 * (p21 - p01) + (p22 - p02);                     /* cv2.Sobel dy, ksize 3 */
+    } else if (WRAP) {                                                          /* np.gradient's interior form at every pixel */
+        zx = (NMV(y, nm_wrap_next(x, w)) - NMV(y, nm_wrap_prev(x, w))) / 2.0;
+        zy = (NMV(nm_wrap_next(y, h), x) - NMV(nm_wrap_prev(y, h), x)) / 2.0;
     } else {                                                                    /* np.gradient, :31 */
         if (w == 1) zx = 0.0;
         else if (x == 0) zx = NMV(y, 1) - NMV(y, 0);
@@ -147,7 +166,7 @@ __global__ void k_nm_check_sqrt_rcp(unsigned long long k0, unsigned long long st
 // Four pixels per lane (w % 4 == 0): the three input rows arrive as one aligned 8-byte load each plus the two edge columns,
 // the 12 output bytes leave as three aligned 32-bit stores (round 1: one pixel per lane, three single-byte stores -- 0.20 ms
 // per 32 x 1024^2 = 10 % of the HBM roofline).
-template <int SOBEL3>
+template <int SOBEL3, int WRAP>
 __global__ __launch_bounds__(NM_BX * NM_BY) void k_normalmap_fused4(const uint16_t *__restrict__ depth, int h, int w, int invert,
                                                                     uint8_t *__restrict__ out)
 {
@@ -157,9 +176,13 @@ __global__ __launch_bounds__(NM_BX * NM_BY) void k_normalmap_fused4(const uint16
     if (x0 >= w || y >= h) return;
     const uint16_t *d = depth + (size_t)img * h * w;
     const double sgn = invert ? 1.0 : -1.0;                                                 /* :20: depthmap * (-1.0) unless inverted */
-    // rows y-1, y, y+1 and columns x0-1 .. x0+4; outside the image: BORDER_REFLECT_101 for Sobel, clamped (unused) for gradient
+    // rows y-1, y, y+1 and columns x0-1 .. x0+4; outside the image: BORDER_REFLECT_101 for Sobel, clamped (unused) for gradient;
+    // WRAP: the row / column on the opposite side (x0 and x0 + 3 are inside the image: only x0 - 1 and x0 + 4 can leave it)
     int ry[3], cl, cr;
-    if (SOBEL3) {
+    if (WRAP) {
+        ry[0] = nm_wrap_prev(y, h); ry[2] = nm_wrap_next(y, h);
+        cl = x0 > 0 ? x0 - 1 : w - 1; cr = x0 + 4 < w ? x0 + 4 : 0;
+    } else if (SOBEL3) {
         ry[0] = nm_reflect101(y - 1, h); ry[2] = nm_reflect101(y + 1, h);
         cl = nm_reflect101(x0 - 1, w); cr = nm_reflect101(x0 + 4, w);
     } else {
@@ -184,6 +207,9 @@ __global__ __launch_bounds__(NM_BX * NM_BY) void k_normalmap_fused4(const uint16
         if (SOBEL3) {
             Zx = (e[0][i + 2] - e[0][i]) + 2 * (e[1][i + 2] - e[1][i]) + (e[2][i + 2] - e[2][i]);        /* cv2.Sobel dx, ksize 3 */
             Zy = (e[2][i] - e[0][i]) + 2 * (e[2][i + 1] - e[0][i + 1]) + (e[2][i + 2] - e[0][i + 2]);    /* cv2.Sobel dy, ksize 3 */
+        } else if (WRAP) {                                                                               /* halved central differences everywhere */
+            Zx = e[1][i + 2] - e[1][i]; kx *= 0.5;
+            Zy = e[2][i + 1] - e[0][i + 1]; ky *= 0.5;
         } else {                                                                                         /* np.gradient, :31 */
             if (x == 0) Zx = e[1][i + 2] - e[1][i + 1];
             else if (x == w - 1) Zx = e[1][i + 1] - e[1][i];
@@ -213,7 +239,8 @@ __global__ __launch_bounds__(256) void k_nm_load(const T *__restrict__ depth, in
 }
 
 // one separable pass along x (AXIS 0) or y (AXIS 1): out = sum_k cf[k] * in[reflect101(pos + k - r)]
-template <int AXIS>
+// (WRAP: in[(pos + k - r) mod size] -- one modulo for the first tap, then a step with a wrap per tap)
+template <int AXIS, int WRAP>
 __global__ __launch_bounds__(256) void k_nm_sep(const double *__restrict__ in, double *__restrict__ out, int h, int w, NmKernel K)
 {
     const int img = blockIdx.z;
@@ -223,15 +250,26 @@ __global__ __launch_bounds__(256) void k_nm_sep(const double *__restrict__ in, d
     const double *p = in + (size_t)img * h * w;
     const int r = K.n / 2;
     double acc = 0.0;
-    for (int k = 0; k < K.n; k++) {
-        double v;
-        if (AXIS == 0) v = p[(size_t)y * w + nm_reflect101(x + k - r, w)];
-        else v = p[(size_t)nm_reflect101(y + k - r, h) * w + x];
-        acc = acc + K.cf[k] * v;
+    if (WRAP) {
+        const int size = AXIS == 0 ? w : h;
+        int j = nm_mod((AXIS == 0 ? x : y) - r, size);
+        for (int k = 0; k < K.n; k++) {
+            const double v = AXIS == 0 ? p[(size_t)y * w + j] : p[(size_t)j * w + x];
+            acc = acc + K.cf[k] * v;
+            j = nm_wrap_next(j, size);
+        }
+    } else {
+        for (int k = 0; k < K.n; k++) {
+            double v;
+            if (AXIS == 0) v = p[(size_t)y * w + nm_reflect101(x + k - r, w)];
+            else v = p[(size_t)nm_reflect101(y + k - r, h) * w + x];
+            acc = acc + K.cf[k] * v;
+        }
     }
     out[(size_t)img * h * w + (size_t)y * w + x] = acc;
 }
 
+template <int WRAP>
 __global__ __launch_bounds__(256) void k_nm_gradient(const double *__restrict__ in, double *__restrict__ zx, double *__restrict__ zy, int h, int w)
 {
     const int img = blockIdx.z;
@@ -241,14 +279,19 @@ __global__ __launch_bounds__(256) void k_nm_gradient(const double *__restrict__ 
     const double *p = in + (size_t)img * h * w;
 #define PV(yy, xx) p[(size_t)(yy) * w + (xx)]
     double gx, gy;
-    if (w == 1) gx = 0.0;
-    else if (x == 0) gx = PV(y, 1) - PV(y, 0);
-    else if (x == w - 1) gx = PV(y, w - 1) - PV(y, w - 2);
-    else gx = (PV(y, x + 1) - PV(y, x - 1)) / 2.0;
-    if (h == 1) gy = 0.0;
-    else if (y == 0) gy = PV(1, x) - PV(0, x);
-    else if (y == h - 1) gy = PV(h - 1, x) - PV(h - 2, x);
-    else gy = (PV(y + 1, x) - PV(y - 1, x)) / 2.0;
+    if (WRAP) {
+        gx = (PV(y, nm_wrap_next(x, w)) - PV(y, nm_wrap_prev(x, w))) / 2.0;
+        gy = (PV(nm_wrap_next(y, h), x) - PV(nm_wrap_prev(y, h), x)) / 2.0;
+    } else {
+        if (w == 1) gx = 0.0;
+        else if (x == 0) gx = PV(y, 1) - PV(y, 0);
+        else if (x == w - 1) gx = PV(y, w - 1) - PV(y, w - 2);
+        else gx = (PV(y, x + 1) - PV(y, x - 1)) / 2.0;
+        if (h == 1) gy = 0.0;
+        else if (y == 0) gy = PV(1, x) - PV(0, x);
+        else if (y == h - 1) gy = PV(h - 1, x) - PV(h - 2, x);
+        else gy = (PV(y + 1, x) - PV(y - 1, x)) / 2.0;
+    }
 #undef PV
     const size_t o = (size_t)img * h * w + (size_t)y * w + x;
     zx[o] = gx; zy[o] = gy;
@@ -331,6 +374,7 @@ static int nm_sobel(int ksize, int order, NmKernel *K)
     return 0;
 }
 
+template <int WRAP>
 static int nm_run(ds_ctx *ctx, const void *depth_any, int is_f64, int n, int h, int w, int pre_blur,
                   int sobel_ksize, int post_blur, int invert, uint8_t *out, void *stream)
 {
@@ -356,14 +400,14 @@ static int nm_run(ds_ctx *ctx, const void *depth_any, int is_f64, int n, int h, 
         if ((w & 3) == 0 && w >= 4 && h >= 2 && (((uintptr_t)depth) & 7) == 0 && (((uintptr_t)out) & 3) == 0 && !getenv("DS_NM_SCALAR")) {
             dim3 grid4((w / 4 + NM_BX - 1) / NM_BX, grid.y, n);
             const int kt = ds_kt_begin(ctx, DS_KT_NORMALMAP, st);
-            if (sobel_ksize == 3) hipLaunchKernelGGL(k_normalmap_fused4<1>, grid4, block, 0, st, depth, h, w, invert ? 1 : 0, out);
-            else hipLaunchKernelGGL(k_normalmap_fused4<0>, grid4, block, 0, st, depth, h, w, invert ? 1 : 0, out);
+            if (sobel_ksize == 3) hipLaunchKernelGGL((k_normalmap_fused4<1, WRAP>), grid4, block, 0, st, depth, h, w, invert ? 1 : 0, out);
+            else hipLaunchKernelGGL((k_normalmap_fused4<0, WRAP>), grid4, block, 0, st, depth, h, w, invert ? 1 : 0, out);
             ds_kt_end(ctx, DS_KT_NORMALMAP, kt, st);
             DS_HIP_CHECK(hipGetLastError());
             return DS_OK;
         }
-        if (sobel_ksize == 3) hipLaunchKernelGGL(k_normalmap_fused<1>, grid, block, 0, st, depth, h, w, invert ? 1 : 0, out);
-        else hipLaunchKernelGGL(k_normalmap_fused<0>, grid, block, 0, st, depth, h, w, invert ? 1 : 0, out);
+        if (sobel_ksize == 3) hipLaunchKernelGGL((k_normalmap_fused<1, WRAP>), grid, block, 0, st, depth, h, w, invert ? 1 : 0, out);
+        else hipLaunchKernelGGL((k_normalmap_fused<0, WRAP>), grid, block, 0, st, depth, h, w, invert ? 1 : 0, out);
         DS_HIP_CHECK(hipGetLastError());
         return DS_OK;
     }
@@ -381,26 +425,26 @@ static int nm_run(ds_ctx *ctx, const void *depth_any, int is_f64, int n, int h, 
     NmKernel G, KD, KS;
     if (pre_blur > 0) {                                            // :23-24
         nm_gaussian(pre_blur, (double)pre_blur, &G);
-        hipLaunchKernelGGL(k_nm_sep<0>, g2, dim3(256), 0, st, A, B, h, w, G);
-        hipLaunchKernelGGL(k_nm_sep<1>, g2, dim3(256), 0, st, B, A, h, w, G);
+        hipLaunchKernelGGL((k_nm_sep<0, WRAP>), g2, dim3(256), 0, st, A, B, h, w, G);
+        hipLaunchKernelGGL((k_nm_sep<1, WRAP>), g2, dim3(256), 0, st, B, A, h, w, G);
     }
     // gradients: zx -> C, zy -> D
     if (sobel_ksize > 0) {                                         // :27-29
         DS_REQUIRE(nm_sobel(sobel_ksize, 1, &KD) == 0 && nm_sobel(sobel_ksize, 0, &KS) == 0, DS_EUNSUPPORTED, "ds_normalmap: Sobel size");
-        hipLaunchKernelGGL(k_nm_sep<0>, g2, dim3(256), 0, st, A, B, h, w, KD);
-        hipLaunchKernelGGL(k_nm_sep<1>, g2, dim3(256), 0, st, B, C, h, w, KS);
-        hipLaunchKernelGGL(k_nm_sep<0>, g2, dim3(256), 0, st, A, B, h, w, KS);
-        hipLaunchKernelGGL(k_nm_sep<1>, g2, dim3(256), 0, st, B, D, h, w, KD);
+        hipLaunchKernelGGL((k_nm_sep<0, WRAP>), g2, dim3(256), 0, st, A, B, h, w, KD);
+        hipLaunchKernelGGL((k_nm_sep<1, WRAP>), g2, dim3(256), 0, st, B, C, h, w, KS);
+        hipLaunchKernelGGL((k_nm_sep<0, WRAP>), g2, dim3(256), 0, st, A, B, h, w, KS);
+        hipLaunchKernelGGL((k_nm_sep<1, WRAP>), g2, dim3(256), 0, st, B, D, h, w, KD);
     } else {
-        hipLaunchKernelGGL(k_nm_gradient, g2, dim3(256), 0, st, A, C, D, h, w);
+        hipLaunchKernelGGL(k_nm_gradient<WRAP>, g2, dim3(256), 0, st, A, C, D, h, w);
     }
     hipLaunchKernelGGL(k_nm_normalize_first, dim3(nb), dim3(256), 0, st, C, D, E, count);
     if (post_blur > 0) {                                           // :42-48
         nm_gaussian(post_blur, (double)post_blur, &G);
         double *planes[3] = { C, D, E };
         for (int k = 0; k < 3; k++) {
-            hipLaunchKernelGGL(k_nm_sep<0>, g2, dim3(256), 0, st, planes[k], B, h, w, G);
-            hipLaunchKernelGGL(k_nm_sep<1>, g2, dim3(256), 0, st, B, planes[k], h, w, G);
+            hipLaunchKernelGGL((k_nm_sep<0, WRAP>), g2, dim3(256), 0, st, planes[k], B, h, w, G);
+            hipLaunchKernelGGL((k_nm_sep<1, WRAP>), g2, dim3(256), 0, st, B, planes[k], h, w, G);
         }
     }
     hipLaunchKernelGGL(k_nm_finish, dim3(nb), dim3(256), 0, st, C, D, E, count, post_blur > 0 ? 1 : 0, out);
@@ -411,7 +455,13 @@ static int nm_run(ds_ctx *ctx, const void *depth_any, int is_f64, int n, int h, 
 DS_API int ds_normalmap(ds_ctx *ctx, const uint16_t *depth, int n, int h, int w, int pre_blur,
                         int sobel_ksize, int post_blur, int invert, uint8_t *out, void *stream)
 {
-    return nm_run(ctx, depth, 0, n, h, w, pre_blur, sobel_ksize, post_blur, invert, out, stream);
+    return nm_run<0>(ctx, depth, 0, n, h, w, pre_blur, sobel_ksize, post_blur, invert, out, stream);
+}
+
+DS_API int ds_normalmap_wrap(ds_ctx *ctx, const uint16_t *depth, int n, int h, int w, int pre_blur,
+                             int sobel_ksize, int post_blur, int invert, uint8_t *out, void *stream)
+{
+    return nm_run<1>(ctx, depth, 0, n, h, w, pre_blur, sobel_ksize, post_blur, invert, out, stream);
 }
 
 // float32 depth with sobel_gradient None / <= 0 (src/normalmap_generation.py:31): the one combination the reference runs in
@@ -419,6 +469,7 @@ DS_API int ds_normalmap(ds_ctx *ctx, const uint16_t *depth, int n, int h, int w,
 // (x * x element-wise, the three squares added left to right, sqrt), the three divisions and `+= 1; /= 2; * 256; clip` are all
 // float32 operations, each correctly rounded (IEEE binary32; hipcc's default float32 division and sqrt are the correctly
 // rounded ones, and the library is built with -ffp-contract=off): one fused pass, bit-identical to numpy.
+template <int WRAP>
 __global__ __launch_bounds__(256) void k_nm_gradient_f32(const float *__restrict__ depth, int h, int w, int invert, uint8_t *__restrict__ out)
 {
     const int img = blockIdx.z;
@@ -429,12 +480,17 @@ __global__ __launch_bounds__(256) void k_nm_gradient_f32(const float *__restrict
     const float sgn = invert ? 1.0f : -1.0f;
 #define PV(yy, xx) ((p[(size_t)(yy) * w + (xx)] * sgn) / 256.0f)
     float gx, gy;
-    if (x == 0) gx = (PV(y, 1) - PV(y, 0)) / 1.0f;
-    else if (x == w - 1) gx = (PV(y, w - 1) - PV(y, w - 2)) / 1.0f;
-    else gx = (PV(y, x + 1) - PV(y, x - 1)) / 2.0f;
-    if (y == 0) gy = (PV(1, x) - PV(0, x)) / 1.0f;
-    else if (y == h - 1) gy = (PV(h - 1, x) - PV(h - 2, x)) / 1.0f;
-    else gy = (PV(y + 1, x) - PV(y - 1, x)) / 2.0f;
+    if (WRAP) {
+        gx = (PV(y, nm_wrap_next(x, w)) - PV(y, nm_wrap_prev(x, w))) / 2.0f;
+        gy = (PV(nm_wrap_next(y, h), x) - PV(nm_wrap_prev(y, h), x)) / 2.0f;
+    } else {
+        if (x == 0) gx = (PV(y, 1) - PV(y, 0)) / 1.0f;
+        else if (x == w - 1) gx = (PV(y, w - 1) - PV(y, w - 2)) / 1.0f;
+        else gx = (PV(y, x + 1) - PV(y, x - 1)) / 2.0f;
+        if (y == 0) gy = (PV(1, x) - PV(0, x)) / 1.0f;
+        else if (y == h - 1) gy = (PV(h - 1, x) - PV(h - 2, x)) / 1.0f;
+        else gy = (PV(y + 1, x) - PV(y - 1, x)) / 2.0f;
+    }
 #undef PV
     const float a = gx, b = -gy, c = 1.0f;
     float s = a * a;
@@ -453,16 +509,27 @@ __global__ __launch_bounds__(256) void k_nm_gradient_f32(const float *__restrict
     }
 }
 
-DS_API int ds_normalmap_gradient_f32(ds_ctx *ctx, const float *depth, int n, int h, int w, int invert, uint8_t *out, void *stream)
+template <int WRAP>
+static int nm_gradient_f32(ds_ctx *ctx, const float *depth, int n, int h, int w, int invert, uint8_t *out, void *stream)
 {
     DS_REQUIRE(ctx && depth && out, DS_EINVAL, "ds_normalmap_gradient_f32: null argument");
     DS_REQUIRE(n > 0 && n <= 65535 && h >= 2 && w >= 2, DS_EINVAL, "ds_normalmap_gradient_f32: np.gradient needs at least 2 samples per axis (n=%d h=%d w=%d)", n, h, w);
     DS_HIP_CHECK(hipSetDevice(ctx->device));
     dim3 g2((w + 63) / 64, (h + 3) / 4, n);
     DS_REQUIRE(g2.y <= 65535, DS_EUNSUPPORTED, "ds_normalmap_gradient_f32: image too tall");
-    hipLaunchKernelGGL(k_nm_gradient_f32, g2, dim3(256), 0, (hipStream_t)stream, depth, h, w, invert ? 1 : 0, out);
+    hipLaunchKernelGGL(k_nm_gradient_f32<WRAP>, g2, dim3(256), 0, (hipStream_t)stream, depth, h, w, invert ? 1 : 0, out);
     DS_HIP_CHECK(hipGetLastError());
     return DS_OK;
+}
+
+DS_API int ds_normalmap_gradient_f32(ds_ctx *ctx, const float *depth, int n, int h, int w, int invert, uint8_t *out, void *stream)
+{
+    return nm_gradient_f32<0>(ctx, depth, n, h, w, invert, out, stream);
+}
+
+DS_API int ds_normalmap_gradient_f32_wrap(ds_ctx *ctx, const float *depth, int n, int h, int w, int invert, uint8_t *out, void *stream)
+{
+    return nm_gradient_f32<1>(ctx, depth, n, h, w, invert, out, stream);
 }
 
 // float16 depth with sobel_gradient None / <= 0 and no blur (round 6): numpy keeps float16 from end to end (:20-21 `* (-1.0)` and
@@ -475,6 +542,7 @@ DS_API int ds_normalmap_gradient_f32(ds_ctx *ctx, const float *depth, int n, int
 // half-rounded chain differ: a CPU test holds numpy to it).
 __device__ __forceinline__ float nm_r16(float x) { return (float)(_Float16)x; }
 
+template <int WRAP>
 __global__ __launch_bounds__(256) void k_nm_gradient_f16(const _Float16 *__restrict__ depth, int h, int w, int invert, uint8_t *__restrict__ out)
 {
     const int img = blockIdx.z;
@@ -485,12 +553,17 @@ __global__ __launch_bounds__(256) void k_nm_gradient_f16(const _Float16 *__restr
     const float sgn = invert ? 1.0f : -1.0f;
 #define PV(yy, xx) nm_r16(nm_r16((float)p[(size_t)(yy) * w + (xx)] * sgn) / 256.0f)
     float gx, gy;
-    if (x == 0) gx = nm_r16(nm_r16(PV(y, 1) - PV(y, 0)) / 1.0f);
-    else if (x == w - 1) gx = nm_r16(nm_r16(PV(y, w - 1) - PV(y, w - 2)) / 1.0f);
-    else gx = nm_r16(nm_r16(PV(y, x + 1) - PV(y, x - 1)) / 2.0f);
-    if (y == 0) gy = nm_r16(nm_r16(PV(1, x) - PV(0, x)) / 1.0f);
-    else if (y == h - 1) gy = nm_r16(nm_r16(PV(h - 1, x) - PV(h - 2, x)) / 1.0f);
-    else gy = nm_r16(nm_r16(PV(y + 1, x) - PV(y - 1, x)) / 2.0f);
+    if (WRAP) {
+        gx = nm_r16(nm_r16(PV(y, nm_wrap_next(x, w)) - PV(y, nm_wrap_prev(x, w))) / 2.0f);
+        gy = nm_r16(nm_r16(PV(nm_wrap_next(y, h), x) - PV(nm_wrap_prev(y, h), x)) / 2.0f);
+    } else {
+        if (x == 0) gx = nm_r16(nm_r16(PV(y, 1) - PV(y, 0)) / 1.0f);
+        else if (x == w - 1) gx = nm_r16(nm_r16(PV(y, w - 1) - PV(y, w - 2)) / 1.0f);
+        else gx = nm_r16(nm_r16(PV(y, x + 1) - PV(y, x - 1)) / 2.0f);
+        if (y == 0) gy = nm_r16(nm_r16(PV(1, x) - PV(0, x)) / 1.0f);
+        else if (y == h - 1) gy = nm_r16(nm_r16(PV(h - 1, x) - PV(h - 2, x)) / 1.0f);
+        else gy = nm_r16(nm_r16(PV(y + 1, x) - PV(y - 1, x)) / 2.0f);
+    }
 #undef PV
     const float a = gx, b = -gy, c = 1.0f;
     const float sa = nm_r16(a * a), sb = nm_r16(b * b), sc = nm_r16(c * c);
@@ -510,16 +583,27 @@ __global__ __launch_bounds__(256) void k_nm_gradient_f16(const _Float16 *__restr
     }
 }
 
-DS_API int ds_normalmap_gradient_f16(ds_ctx *ctx, const void *depth, int n, int h, int w, int invert, uint8_t *out, void *stream)
+template <int WRAP>
+static int nm_gradient_f16(ds_ctx *ctx, const void *depth, int n, int h, int w, int invert, uint8_t *out, void *stream)
 {
     DS_REQUIRE(ctx && depth && out, DS_EINVAL, "ds_normalmap_gradient_f16: null argument");
     DS_REQUIRE(n > 0 && n <= 65535 && h >= 2 && w >= 2, DS_EINVAL, "ds_normalmap_gradient_f16: np.gradient needs at least 2 samples per axis (n=%d h=%d w=%d)", n, h, w);
     DS_HIP_CHECK(hipSetDevice(ctx->device));
     dim3 g2((w + 63) / 64, (h + 3) / 4, n);
     DS_REQUIRE(g2.y <= 65535, DS_EUNSUPPORTED, "ds_normalmap_gradient_f16: image too tall");
-    hipLaunchKernelGGL(k_nm_gradient_f16, g2, dim3(256), 0, (hipStream_t)stream, (const _Float16 *)depth, h, w, invert ? 1 : 0, out);
+    hipLaunchKernelGGL(k_nm_gradient_f16<WRAP>, g2, dim3(256), 0, (hipStream_t)stream, (const _Float16 *)depth, h, w, invert ? 1 : 0, out);
     DS_HIP_CHECK(hipGetLastError());
     return DS_OK;
+}
+
+DS_API int ds_normalmap_gradient_f16(ds_ctx *ctx, const void *depth, int n, int h, int w, int invert, uint8_t *out, void *stream)
+{
+    return nm_gradient_f16<0>(ctx, depth, n, h, w, invert, out, stream);
+}
+
+DS_API int ds_normalmap_gradient_f16_wrap(ds_ctx *ctx, const void *depth, int n, int h, int w, int invert, uint8_t *out, void *stream)
+{
+    return nm_gradient_f16<1>(ctx, depth, n, h, w, invert, out, stream);
 }
 
 // float32 depth with np.gradient AND a Gaussian blur in front of and / or behind it (round 6): the reference hands float32 arrays to
@@ -537,7 +621,7 @@ __global__ __launch_bounds__(256) void k_nm_load_f32(const float *__restrict__ d
         plane[i] = (depth[i] * sgn) / 256.0f;
 }
 
-template <int AXIS>
+template <int AXIS, int WRAP>
 __global__ __launch_bounds__(256) void k_nm_sep_f32(const float *__restrict__ in, float *__restrict__ out, int h, int w, NmKernelF K)
 {
     const int img = blockIdx.z;
@@ -547,16 +631,27 @@ __global__ __launch_bounds__(256) void k_nm_sep_f32(const float *__restrict__ in
     const float *p = in + (size_t)img * h * w;
     const int r = K.n / 2;
     float acc = 0.0f;
-    for (int k = 0; k < K.n; k++) {
-        float v;
-        if (AXIS == 0) v = p[(size_t)y * w + nm_reflect101(x + k - r, w)];
-        else v = p[(size_t)nm_reflect101(y + k - r, h) * w + x];
-        acc = acc + K.cf[k] * v;
+    if (WRAP) {
+        const int size = AXIS == 0 ? w : h;
+        int j = nm_mod((AXIS == 0 ? x : y) - r, size);
+        for (int k = 0; k < K.n; k++) {
+            const float v = AXIS == 0 ? p[(size_t)y * w + j] : p[(size_t)j * w + x];
+            acc = acc + K.cf[k] * v;
+            j = nm_wrap_next(j, size);
+        }
+    } else {
+        for (int k = 0; k < K.n; k++) {
+            float v;
+            if (AXIS == 0) v = p[(size_t)y * w + nm_reflect101(x + k - r, w)];
+            else v = p[(size_t)nm_reflect101(y + k - r, h) * w + x];
+            acc = acc + K.cf[k] * v;
+        }
     }
     out[(size_t)img * h * w + (size_t)y * w + x] = acc;
 }
 
 // np.gradient (:31) of the (blurred) plane and the first normalisation (:33-39), float32 like numpy: planes n0, n1, n2 out
+template <int WRAP>
 __global__ __launch_bounds__(256) void k_nm_gradnorm_f32(const float *__restrict__ in, float *__restrict__ n0, float *__restrict__ n1,
                                                          float *__restrict__ n2, int h, int w)
 {
@@ -567,12 +662,17 @@ __global__ __launch_bounds__(256) void k_nm_gradnorm_f32(const float *__restrict
     const float *p = in + (size_t)img * h * w;
 #define PV(yy, xx) p[(size_t)(yy) * w + (xx)]
     float gx, gy;
-    if (x == 0) gx = (PV(y, 1) - PV(y, 0)) / 1.0f;
-    else if (x == w - 1) gx = (PV(y, w - 1) - PV(y, w - 2)) / 1.0f;
-    else gx = (PV(y, x + 1) - PV(y, x - 1)) / 2.0f;
-    if (y == 0) gy = (PV(1, x) - PV(0, x)) / 1.0f;
-    else if (y == h - 1) gy = (PV(h - 1, x) - PV(h - 2, x)) / 1.0f;
-    else gy = (PV(y + 1, x) - PV(y - 1, x)) / 2.0f;
+    if (WRAP) {
+        gx = (PV(y, nm_wrap_next(x, w)) - PV(y, nm_wrap_prev(x, w))) / 2.0f;
+        gy = (PV(nm_wrap_next(y, h), x) - PV(nm_wrap_prev(y, h), x)) / 2.0f;
+    } else {
+        if (x == 0) gx = (PV(y, 1) - PV(y, 0)) / 1.0f;
+        else if (x == w - 1) gx = (PV(y, w - 1) - PV(y, w - 2)) / 1.0f;
+        else gx = (PV(y, x + 1) - PV(y, x - 1)) / 2.0f;
+        if (y == 0) gy = (PV(1, x) - PV(0, x)) / 1.0f;
+        else if (y == h - 1) gy = (PV(h - 1, x) - PV(h - 2, x)) / 1.0f;
+        else gy = (PV(y + 1, x) - PV(y - 1, x)) / 2.0f;
+    }
 #undef PV
     const float a = gx, b = -gy, c = 1.0f;
     float s = a * a;
@@ -620,14 +720,15 @@ static void nm_gaussian_f32(int ksize, double sigma, NmKernelF *K)   // getGauss
     for (int i = 0; i < ksize; i++) K->cf[i] = (float)(K->cf[i] * inv);
 }
 
-DS_API int ds_normalmap_gradient_blur_f32(ds_ctx *ctx, const float *depth, int n, int h, int w, int pre_blur, int post_blur, int invert,
-                                          uint8_t *out, void *stream)
+template <int WRAP>
+static int nm_gradient_blur_f32(ds_ctx *ctx, const float *depth, int n, int h, int w, int pre_blur, int post_blur, int invert,
+                                uint8_t *out, void *stream)
 {
     DS_REQUIRE(ctx && depth && out, DS_EINVAL, "ds_normalmap_gradient_blur_f32: null argument");
     DS_REQUIRE(n > 0 && n <= 65535 && h >= 2 && w >= 2, DS_EINVAL, "ds_normalmap_gradient_blur_f32: np.gradient needs at least 2 samples per axis (n=%d h=%d w=%d)", n, h, w);
     if (pre_blur < 0) pre_blur = 0;
     if (post_blur < 0) post_blur = 0;
-    if (pre_blur == 0 && post_blur == 0) return ds_normalmap_gradient_f32(ctx, depth, n, h, w, invert, out, stream);
+    if (pre_blur == 0 && post_blur == 0) return nm_gradient_f32<WRAP>(ctx, depth, n, h, w, invert, out, stream);
     DS_REQUIRE((pre_blur == 0 || (pre_blur & 1)) && (post_blur == 0 || (post_blur & 1)), DS_EINVAL,
                "ds_normalmap_gradient_blur_f32: Gaussian kernel sizes must be odd (cv2.GaussianBlur asserts)");
     DS_REQUIRE(pre_blur <= NM_MAXK && post_blur <= NM_MAXK, DS_EUNSUPPORTED, "ds_normalmap_gradient_blur_f32: kernel sizes above %d are not supported", NM_MAXK);
@@ -644,16 +745,16 @@ DS_API int ds_normalmap_gradient_blur_f32(ds_ctx *ctx, const float *depth, int n
     NmKernelF G;
     if (pre_blur > 0) {                                            // :23-24
         nm_gaussian_f32(pre_blur, (double)pre_blur, &G);
-        hipLaunchKernelGGL(k_nm_sep_f32<0>, g2, dim3(256), 0, st, A, B, h, w, G);
-        hipLaunchKernelGGL(k_nm_sep_f32<1>, g2, dim3(256), 0, st, B, A, h, w, G);
+        hipLaunchKernelGGL((k_nm_sep_f32<0, WRAP>), g2, dim3(256), 0, st, A, B, h, w, G);
+        hipLaunchKernelGGL((k_nm_sep_f32<1, WRAP>), g2, dim3(256), 0, st, B, A, h, w, G);
     }
-    hipLaunchKernelGGL(k_nm_gradnorm_f32, g2, dim3(256), 0, st, A, C, D, E, h, w);
+    hipLaunchKernelGGL(k_nm_gradnorm_f32<WRAP>, g2, dim3(256), 0, st, A, C, D, E, h, w);
     if (post_blur > 0) {                                           // :42-48
         nm_gaussian_f32(post_blur, (double)post_blur, &G);
         float *planes[3] = { C, D, E };
         for (int k = 0; k < 3; k++) {
-            hipLaunchKernelGGL(k_nm_sep_f32<0>, g2, dim3(256), 0, st, planes[k], B, h, w, G);
-            hipLaunchKernelGGL(k_nm_sep_f32<1>, g2, dim3(256), 0, st, B, planes[k], h, w, G);
+            hipLaunchKernelGGL((k_nm_sep_f32<0, WRAP>), g2, dim3(256), 0, st, planes[k], B, h, w, G);
+            hipLaunchKernelGGL((k_nm_sep_f32<1, WRAP>), g2, dim3(256), 0, st, B, planes[k], h, w, G);
         }
     }
     hipLaunchKernelGGL(k_nm_finish_f32, dim3(nb), dim3(256), 0, st, C, D, E, count, post_blur > 0 ? 1 : 0, out);
@@ -661,12 +762,30 @@ DS_API int ds_normalmap_gradient_blur_f32(ds_ctx *ctx, const float *depth, int n
     return DS_OK;
 }
 
+DS_API int ds_normalmap_gradient_blur_f32(ds_ctx *ctx, const float *depth, int n, int h, int w, int pre_blur, int post_blur, int invert,
+                                          uint8_t *out, void *stream)
+{
+    return nm_gradient_blur_f32<0>(ctx, depth, n, h, w, pre_blur, post_blur, invert, out, stream);
+}
+
+DS_API int ds_normalmap_gradient_blur_f32_wrap(ds_ctx *ctx, const float *depth, int n, int h, int w, int pre_blur, int post_blur, int invert,
+                                               uint8_t *out, void *stream)
+{
+    return nm_gradient_blur_f32<1>(ctx, depth, n, h, w, pre_blur, post_blur, invert, out, stream);
+}
+
 // Any other real dtype of the reference's `depthmap` argument (:20-21 promote it to float64; the host casts): the separable
 // float64 passes for every kernel size (general float64 data has no exact 3x3 shortcut).
 DS_API int ds_normalmap_f64(ds_ctx *ctx, const double *depth, int n, int h, int w, int pre_blur,
                             int sobel_ksize, int post_blur, int invert, uint8_t *out, void *stream)
 {
-    return nm_run(ctx, depth, 1, n, h, w, pre_blur, sobel_ksize, post_blur, invert, out, stream);
+    return nm_run<0>(ctx, depth, 1, n, h, w, pre_blur, sobel_ksize, post_blur, invert, out, stream);
+}
+
+DS_API int ds_normalmap_f64_wrap(ds_ctx *ctx, const double *depth, int n, int h, int w, int pre_blur,
+                                 int sobel_ksize, int post_blur, int invert, uint8_t *out, void *stream)
+{
+    return nm_run<1>(ctx, depth, 1, n, h, w, pre_blur, sobel_ksize, post_blur, invert, out, stream);
 }
 
 DS_API int ds_normalmap_selfcheck(ds_ctx *ctx, unsigned long long k0, unsigned long long stride, unsigned long long count,

@@ -26,6 +26,7 @@ EXPORTS = [
     "ds_linear_shuffle", "ds_linear_readout", "ds_kernel_timer_enable", "ds_kernel_timer_read", "ds_kernel_timer_read_each", "ds_group_norm_nchw",
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
+    "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
 ]
 
 
@@ -71,6 +72,8 @@ def lib():
             L.ds_normalmap_gradient_f32.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
             L.ds_normalmap_gradient_f16.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
             L.ds_normalmap_gradient_blur_f32.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
+            for name in ("ds_normalmap", "ds_normalmap_f64", "ds_normalmap_gradient_f32", "ds_normalmap_gradient_f16", "ds_normalmap_gradient_blur_f32"):
+                getattr(L, name + "_wrap").argtypes = getattr(L, name).argtypes
             L.ds_depth_to_u16.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp]
             L.ds_convert_to_i16.argtypes = [vp, vp, ci, i64, vp, vp]
             L.ds_stereo_last_stats.argtypes = [vp, ctypes.POINTER(i64), vp]
@@ -256,35 +259,41 @@ def overlap_red_cyan(im1_ptr, r1, i1, im2_ptr, r2, i2, n, h, w, c, out):
                                      _stream(out)))
 
 
-def normalmap(depth, pre_blur, sobel_ksize, post_blur, invert):
+def normalmap(depth, pre_blur, sobel_ksize, post_blur, invert, wrap=False):
     """depth [n,h,w]: uint16 (the funnel's depth maps; the fused kernel), float64 (any other dtype, cast by the caller), float32
     with np.gradient (the reference's float32 evaluation: ds_normalmap_gradient_f32 / ds_normalmap_gradient_blur_f32) or float16
-    with np.gradient and no blur (numpy's float16 evaluation: ds_normalmap_gradient_f16)."""
+    with np.gradient and no blur (numpy's float16 evaluation: ds_normalmap_gradient_f16).
+    wrap: the depth map is one period of a tiling -- the `_wrap` entry point of the same name (include/depthstereo.h: every tap index
+    modulo the image size, np.gradient's central difference at every pixel) instead of the reference's borders."""
     torch = require_gpu()
     n, h, w = depth.shape
     assert depth.dtype in (torch.uint16, torch.float64, torch.float32, torch.float16) and depth.is_contiguous()
     out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=depth.device)
+    sfx = "_wrap" if wrap else ""
     if depth.dtype == torch.float16:
         assert int(pre_blur) == 0 and int(post_blur) == 0 and int(sobel_ksize) == 0, "float16 depth: np.gradient without blurs only"
-        CALLS["ds_normalmap_gradient_f16"] += 1
-        _check(lib().ds_normalmap_gradient_f16(ctx_for(_dev_index(depth)), depth.data_ptr(), n, h, w, 1 if invert else 0,
-                                               out.data_ptr(), _stream(depth)))
+        name = "ds_normalmap_gradient_f16" + sfx
+        CALLS[name] += 1
+        _check(getattr(lib(), name)(ctx_for(_dev_index(depth)), depth.data_ptr(), n, h, w, 1 if invert else 0,
+                                    out.data_ptr(), _stream(depth)))
         return out
     if depth.dtype == torch.float32:
         assert int(sobel_ksize) == 0, "float32 depth: np.gradient only (cv2.Sobel is fed float64)"
         if int(pre_blur) == 0 and int(post_blur) == 0:
-            CALLS["ds_normalmap_gradient_f32"] += 1
-            _check(lib().ds_normalmap_gradient_f32(ctx_for(_dev_index(depth)), depth.data_ptr(), n, h, w, 1 if invert else 0,
-                                                   out.data_ptr(), _stream(depth)))
+            name = "ds_normalmap_gradient_f32" + sfx
+            CALLS[name] += 1
+            _check(getattr(lib(), name)(ctx_for(_dev_index(depth)), depth.data_ptr(), n, h, w, 1 if invert else 0,
+                                        out.data_ptr(), _stream(depth)))
         else:
-            CALLS["ds_normalmap_gradient_blur_f32"] += 1
-            _check(lib().ds_normalmap_gradient_blur_f32(ctx_for(_dev_index(depth)), depth.data_ptr(), n, h, w, int(pre_blur), int(post_blur),
-                                                        1 if invert else 0, out.data_ptr(), _stream(depth)))
+            name = "ds_normalmap_gradient_blur_f32" + sfx
+            CALLS[name] += 1
+            _check(getattr(lib(), name)(ctx_for(_dev_index(depth)), depth.data_ptr(), n, h, w, int(pre_blur), int(post_blur),
+                                        1 if invert else 0, out.data_ptr(), _stream(depth)))
         return out
-    fn = lib().ds_normalmap if depth.dtype == torch.uint16 else lib().ds_normalmap_f64
-    CALLS["ds_normalmap" if depth.dtype == torch.uint16 else "ds_normalmap_f64"] += 1
-    _check(fn(ctx_for(_dev_index(depth)), depth.data_ptr(), n, h, w, int(pre_blur), int(sobel_ksize),
-              int(post_blur), 1 if invert else 0, out.data_ptr(), _stream(depth)))
+    name = ("ds_normalmap" if depth.dtype == torch.uint16 else "ds_normalmap_f64") + sfx
+    CALLS[name] += 1
+    _check(getattr(lib(), name)(ctx_for(_dev_index(depth)), depth.data_ptr(), n, h, w, int(pre_blur), int(sobel_ksize),
+                                int(post_blur), 1 if invert else 0, out.data_ptr(), _stream(depth)))
     return out
 
 

@@ -438,7 +438,7 @@ def _mark(g, name, stream=None):
     g.setdefault("trace", []).append((name, ev, _time.perf_counter()))
 
 
-def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=None):
+def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=None, normalmap_wrap=False):
     """Enqueue everything a group needs on the current stream -- H2D, network, post-processing, stereo, normal map, heat
     map, D2H into pinned buffers -- and return the handles; nothing here waits for the device except the post-processing
     branches that must know which predictions are flat (one sync per batch) and the percentile bisection of 'Outliers'."""
@@ -604,7 +604,7 @@ def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=Non
                 inp[go.NORMALMAP_PRE_BLUR_KERNEL] if inp[go.NORMALMAP_PRE_BLUR] else None,
                 inp[go.NORMALMAP_SOBEL_KERNEL] if inp[go.NORMALMAP_SOBEL] else None,
                 inp[go.NORMALMAP_POST_BLUR_KERNEL] if inp[go.NORMALMAP_POST_BLUR] else None,
-                inp[go.NORMALMAP_INVERT]), "normalmap")
+                inp[go.NORMALMAP_INVERT], wrap=normalmap_wrap), "normalmap")
         if inp[go.GEN_HEATMAP]:                                                                      # :271-274
             from .heatmap import colorize_batch
             download(colorize_batch(d16), "heatmap")
@@ -878,7 +878,17 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
                                       "(SURVEY.md section 8); use the reference for it")
     if ops is None:
         ops = {}
-    model_holder.update_settings(**ops)
+    # ops['normalmap_wrap'] (not in the reference: its normalmap_generation.py:16 leaves tiling as a TODO): True = the normal map
+    # treats every depth map as one period of a tiling (create_normalmap_batch(wrap=True)); 'tiling' = exactly when TILING_MODE is on;
+    # absent / False = the reference's borders.  It belongs to THIS call: it is taken from `ops` here and does not become a setting
+    # of the model holder, so a later call without it is back to the reference's borders.
+    normalmap_wrap = ops.get('normalmap_wrap', False)
+    if isinstance(normalmap_wrap, str):
+        if normalmap_wrap != 'tiling':
+            raise ValueError("ops['normalmap_wrap'] must be True, False or 'tiling', got %r" % (normalmap_wrap,))
+        normalmap_wrap = bool(inp[go.TILING_MODE])
+    normalmap_wrap = bool(normalmap_wrap)
+    model_holder.update_settings(**{k: v for k, v in ops.items() if k != 'normalmap_wrap'})
 
     torch = _native.require_gpu()        # the hot path has no CPU implementation, whatever COMPUTE_DEVICE says
     device = torch.device('cuda', torch.cuda.current_device())
@@ -908,7 +918,7 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
             # reference's per-image loop (:133-329) would have yielded them before reaching the failing image
             try:
                 _t0 = _time.perf_counter()
-                launched, failure = _launch_group(gi & 1, idxs, inputimages, inputdepthmaps, inp, device, stats), None
+                launched, failure = _launch_group(gi & 1, idxs, inputimages, inputdepthmaps, inp, device, stats, normalmap_wrap), None
                 stats["launch"] = stats.get("launch", 0.0) + (_time.perf_counter() - _t0)
             except Exception as e:          # noqa: BLE001 -- re-raised below, after the results that precede it
                 launched, failure = None, e

@@ -9,13 +9,17 @@ def _ksize(v):
     return int(v) if v is not None and v > 0 else 0
 
 
-def create_normalmap(depthmap, pre_blur=None, sobel_gradient=3, post_blur=None, invert=False):
+def create_normalmap(depthmap, pre_blur=None, sobel_gradient=3, post_blur=None, invert=False, wrap=False):
     """Generates normalmaps (reference: src/normalmap_generation.py:5-56).
     :param depthmap: HxW depthmap: uint16 from the funnel (core.py:262), or any other real array like the reference
     :param pre_blur: Gaussian blur before the gradient, None/<=0 to disable, otherwise kernel size
     :param sobel_gradient: Sobel kernel size, None/<=0 for np.gradient
     :param post_blur: Gaussian blur after the gradient, None/<=0 to disable, otherwise kernel size
     :param invert: depthmap will be inverted before calculating normalmap
+    :param wrap: (not in the reference, whose :16 leaves it as a TODO) the depth map is one period of a tiling: Sobel / Gaussian taps
+        read index modulo size instead of BORDER_REFLECT_101, np.gradient is the central difference at every pixel, so the normal
+        map tiles like the depth map does -- normalmap(np.pad(d, R, mode='wrap'))[R:R+h, R:R+w] bit for bit (R: the summed radii
+        of the passes).  Same dtype rules.  False: the reference's borders, byte for byte
     """
     torch = _native.require_gpu()
     depth = np.asarray(depthmap)
@@ -38,10 +42,12 @@ def create_normalmap(depthmap, pre_blur=None, sobel_gradient=3, post_blur=None, 
             depth = depth.astype(np.float64)
     dev = torch.device('cuda', torch.cuda.current_device())
     d = torch.from_numpy(np.array(depth, order='C')).to(dev).unsqueeze(0)
-    out = create_normalmap_batch(d, pre_blur, sobel_gradient, post_blur, invert)
+    out = create_normalmap_batch(d, pre_blur, sobel_gradient, post_blur, invert, wrap)
     return Image.fromarray(out[0].cpu().numpy())
 
 
-def create_normalmap_batch(depth_u16, pre_blur=None, sobel_gradient=3, post_blur=None, invert=False):
-    """Device-resident batch: uint16 (or float64 / float32 / float16, see _native.normalmap) cuda tensor [N,H,W] -> uint8 cuda tensor [N,H,W,3]."""
-    return _native.normalmap(depth_u16.contiguous(), _ksize(pre_blur), _ksize(sobel_gradient), _ksize(post_blur), bool(invert))
+def create_normalmap_batch(depth_u16, pre_blur=None, sobel_gradient=3, post_blur=None, invert=False, wrap=False):
+    """Device-resident batch: uint16 (or float64 / float32 / float16, see _native.normalmap) cuda tensor [N,H,W] -> uint8 cuda tensor [N,H,W,3].
+    wrap: every image is one period of a tiling (see create_normalmap)."""
+    return _native.normalmap(depth_u16.contiguous(), _ksize(pre_blur), _ksize(sobel_gradient), _ksize(post_blur), bool(invert),
+                             wrap=bool(wrap))
