@@ -218,6 +218,27 @@ int ds_normalmap_gradient_blur_f32_wrap(ds_ctx *ctx, const float *depth, int n, 
                                         uint8_t *out, void *stream);
 
 /*
+ * ds_bilateral_u16 -- edge-preserving pre-filter for uint16 depth maps in front of the normal map ("16 bit deflickering": the
+ * reference leaves it as a TODO, src/normalmap_generation.py:17, and has no implementation; this comment is the definition).
+ * depth [n,h,w] uint16 -> out [n,h,w] float64 in the units of depth; feed out to ds_normalmap_f64[_wrap].
+ *   ws: (2 radius + 1)^2 float64 spatial weights in raster order (dy outer, dx inner, both -radius..radius), made on the host:
+ *       exp(-(dx^2 + dy^2) / (2 sigma_space^2)) where dx^2 + dy^2 <= radius^2, exactly 0.0 outside that circle;
+ *   wr: 65536 float64 range weights, wr[k] = exp(-k^2 / (2 sigma_color^2)), made on the host.  Its argument is the INTEGER
+ *       |D(q) - D(p)|: no exp runs on the device.
+ *   For pixel p: num = den = 0; for every tap t in raster order with ws[t] != 0: q = p + (dy, dx) after the border rule, v = D(q);
+ *       wgt = ws[t] * wr[|D(q) - D(p)|];  num = num + wgt * v (the product rounded, then the sum: no fused multiply-add);
+ *       den = den + wgt;  out(p) = num / den, one IEEE division (the centre tap makes den >= 1).
+ *   Borders: wrap == 0 BORDER_REFLECT_101 (radius < min(h, w) required), wrap != 0 tap index modulo the image size (any size).
+ * One accumulation chain per pixel: a pixel's result does not depend on the tiling of the launch, the batch size or its position in
+ * the batch; a float64 NumPy loop over the taps gives the same bits (tests/normalmap_bilateral_cases.py).
+ * DS_EINVAL: a null pointer; n, h or w <= 0; radius outside 1..15; radius >= min(h, w) without wrap; out overlapping depth; out, ws
+ * or wr not 8-byte aligned (depth: 2-byte).  DS_EUNSUPPORTED: n > 65535 or h > 32 * 65535.  Asynchronous on `stream`; the kernel
+ * timer DS_KT_NORMALMAP brackets the launch.
+ */
+int ds_bilateral_u16(ds_ctx *ctx, const uint16_t *depth, int n, int h, int w, int radius, const double *ws, const double *wr,
+                     int wrap, double *out, void *stream);
+
+/*
  * ds_normalmap_selfcheck -- device self-test of the fused normal-map kernels' arithmetic (tests): their square root and reciprocal
  * are the generic float64 expansions WITHOUT range scaling and special-case fix-ups (dead for n^2 = zx^2 + zy^2 + 1 in [1, 2^22],
  * src/normalmap_generation.py:34-39); the kernel compares them with sqrt() and 1.0 / n on n^2 = K / 2^18, K = k0 + stride * i,

@@ -27,6 +27,7 @@ EXPORTS = [
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
+    "ds_bilateral_u16",
 ]
 
 
@@ -74,6 +75,7 @@ def lib():
             L.ds_normalmap_gradient_blur_f32.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
             for name in ("ds_normalmap", "ds_normalmap_f64", "ds_normalmap_gradient_f32", "ds_normalmap_gradient_f16", "ds_normalmap_gradient_blur_f32"):
                 getattr(L, name + "_wrap").argtypes = getattr(L, name).argtypes
+            L.ds_bilateral_u16.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, ci, vp, vp]
             L.ds_depth_to_u16.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp]
             L.ds_convert_to_i16.argtypes = [vp, vp, ci, i64, vp, vp]
             L.ds_stereo_last_stats.argtypes = [vp, ctypes.POINTER(i64), vp]
@@ -294,6 +296,73 @@ def normalmap(depth, pre_blur, sobel_ksize, post_blur, invert, wrap=False):
     CALLS[name] += 1
     _check(getattr(lib(), name)(ctx_for(_dev_index(depth)), depth.data_ptr(), n, h, w, int(pre_blur), int(sobel_ksize),
                                 int(post_blur), 1 if invert else 0, out.data_ptr(), _stream(depth)))
+    return out
+
+
+_BILATERAL_TABLES = collections.OrderedDict()          # (device index, d, sigma_color, sigma_space) -> (ws, wr) on that device
+_BILATERAL_TABLES_MAX = 4
+_BILATERAL_LOCK = threading.Lock()
+
+
+def bilateral_params(bilateral):
+    """(d, sigma_color, sigma_space) as (int, float, float), or ValueError: d odd in 3..31, both sigmas finite and > 0.  Pure
+    Python (the funnel checks its option with it before any device work)."""
+    try:
+        d, sigma_color, sigma_space = bilateral
+        ok = not isinstance(d, bool) and int(d) == d
+        d, sigma_color, sigma_space = int(d), float(sigma_color), float(sigma_space)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("bilateral must be (d, sigma_color, sigma_space), got %r" % (bilateral,)) from None
+    if not (ok and d % 2 == 1 and 3 <= d <= 31):
+        raise ValueError("bilateral: d must be an odd integer in 3..31, got %r" % (bilateral[0],))
+    if not (0.0 < sigma_color < math.inf and 0.0 < sigma_space < math.inf):
+        raise ValueError("bilateral: sigma_color and sigma_space must be finite and > 0, got %r, %r" % (sigma_color, sigma_space))
+    return d, sigma_color, sigma_space
+
+
+def bilateral_tables(d, sigma_color, sigma_space):
+    """The two host-made tables of ds_bilateral_u16 (include/depthstereo.h), float64: ws (d * d, raster order, exactly 0 outside the
+    circle of radius d // 2) and wr (65536, indexed by the integer |D(q) - D(p)|)."""
+    r = d // 2
+    dy, dx = np.mgrid[-r:r + 1, -r:r + 1]
+    ws = np.where(dx * dx + dy * dy <= r * r, np.exp(-(dx * dx + dy * dy) / (2.0 * sigma_space**2)), 0.0).astype(np.float64).ravel()
+    wr = np.exp(-(np.arange(65536, dtype=np.float64)**2) / (2.0 * sigma_color**2))
+    return ws, wr
+
+
+def bilateral_u16(depth_u16, d, sigma_color, sigma_space, wrap=False):
+    """Bilateral filter of uint16 depth maps [n,h,w] (cuda) -> float64 [n,h,w] in the same units (ds_bilateral_u16: the definition is
+    in include/depthstereo.h).  d: odd window diameter 3..31; sigma_color in uint16 levels; sigma_space in pixels; wrap: tap indices
+    modulo the image size instead of BORDER_REFLECT_101 (which needs d // 2 < min(h, w)).  The tables are made on the host, uploaded
+    once and kept for the last 4 (device, d, sigma_color, sigma_space)."""
+    torch = require_gpu()
+    try:
+        d, sigma_color, sigma_space = bilateral_params((d, sigma_color, sigma_space))
+    except ValueError as e:
+        raise DepthStereoError("bilateral_u16: %s" % e) from None
+    if not (torch.is_tensor(depth_u16) and depth_u16.is_cuda and depth_u16.dtype == torch.uint16 and depth_u16.dim() == 3):
+        raise DepthStereoError("bilateral_u16: depth must be a uint16 cuda tensor [n,h,w] (the range table is indexed by an integer "
+                               "difference), got %s %s" % (getattr(depth_u16, "dtype", type(depth_u16)), tuple(getattr(depth_u16, "shape", ()))))
+    depth_u16 = depth_u16.contiguous()
+    n, h, w = depth_u16.shape
+    if not wrap and d // 2 >= min(h, w):
+        raise DepthStereoError("bilateral_u16: d // 2 = %d must be below min(h, w) = %d without wrap" % (d // 2, min(h, w)))
+    key = (_dev_index(depth_u16), d, sigma_color, sigma_space)
+    with _BILATERAL_LOCK:
+        tabs = _BILATERAL_TABLES.get(key)
+        if tabs is None:
+            ws, wr = bilateral_tables(d, sigma_color, sigma_space)
+            tabs = _BILATERAL_TABLES[key] = (torch.from_numpy(ws).to(depth_u16.device), torch.from_numpy(wr).to(depth_u16.device))
+            while len(_BILATERAL_TABLES) > _BILATERAL_TABLES_MAX:
+                _BILATERAL_TABLES.popitem(last=False)
+        else:
+            _BILATERAL_TABLES.move_to_end(key)
+    for t in tabs:                   # an evicted table may still be read by a launch on this stream: tell the allocator
+        t.record_stream(torch.cuda.current_stream(depth_u16.device))
+    out = torch.empty((n, h, w), dtype=torch.float64, device=depth_u16.device)
+    CALLS["ds_bilateral_u16"] += 1
+    _check(lib().ds_bilateral_u16(ctx_for(_dev_index(depth_u16)), depth_u16.data_ptr(), n, h, w, d // 2, tabs[0].data_ptr(),
+                                  tabs[1].data_ptr(), 1 if wrap else 0, out.data_ptr(), _stream(depth_u16)))
     return out
 
 

@@ -438,7 +438,7 @@ def _mark(g, name, stream=None):
     g.setdefault("trace", []).append((name, ev, _time.perf_counter()))
 
 
-def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=None, normalmap_wrap=False):
+def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=None, normalmap_wrap=False, normalmap_bilateral=None):
     """Enqueue everything a group needs on the current stream -- H2D, network, post-processing, stereo, normal map, heat
     map, D2H into pinned buffers -- and return the handles; nothing here waits for the device except the post-processing
     branches that must know which predictions are flat (one sync per batch) and the percentile bisection of 'Outliers'."""
@@ -604,7 +604,7 @@ def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=Non
                 inp[go.NORMALMAP_PRE_BLUR_KERNEL] if inp[go.NORMALMAP_PRE_BLUR] else None,
                 inp[go.NORMALMAP_SOBEL_KERNEL] if inp[go.NORMALMAP_SOBEL] else None,
                 inp[go.NORMALMAP_POST_BLUR_KERNEL] if inp[go.NORMALMAP_POST_BLUR] else None,
-                inp[go.NORMALMAP_INVERT], wrap=normalmap_wrap), "normalmap")
+                inp[go.NORMALMAP_INVERT], wrap=normalmap_wrap, bilateral=normalmap_bilateral), "normalmap")
         if inp[go.GEN_HEATMAP]:                                                                      # :271-274
             from .heatmap import colorize_batch
             download(colorize_batch(d16), "heatmap")
@@ -888,7 +888,14 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
             raise ValueError("ops['normalmap_wrap'] must be True, False or 'tiling', got %r" % (normalmap_wrap,))
         normalmap_wrap = bool(inp[go.TILING_MODE])
     normalmap_wrap = bool(normalmap_wrap)
-    model_holder.update_settings(**{k: v for k, v in ops.items() if k != 'normalmap_wrap'})
+    # ops['normalmap_bilateral'] (not in the reference either: its normalmap_generation.py:17 leaves "bilateral filtering (16 bit
+    # deflickering)" as a TODO): (d, sigma_color, sigma_space) = the edge-preserving pre-filter of create_normalmap_batch(bilateral=...)
+    # on the funnel's uint16 depth maps; absent / None = off.  An option of THIS call, like normalmap_wrap; a malformed value is a
+    # ValueError here, before any device work.
+    normalmap_bilateral = ops.get('normalmap_bilateral')
+    if normalmap_bilateral is not None:
+        normalmap_bilateral = _native.bilateral_params(normalmap_bilateral)
+    model_holder.update_settings(**{k: v for k, v in ops.items() if k not in ('normalmap_wrap', 'normalmap_bilateral')})
 
     torch = _native.require_gpu()        # the hot path has no CPU implementation, whatever COMPUTE_DEVICE says
     device = torch.device('cuda', torch.cuda.current_device())
@@ -918,7 +925,8 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
             # reference's per-image loop (:133-329) would have yielded them before reaching the failing image
             try:
                 _t0 = _time.perf_counter()
-                launched, failure = _launch_group(gi & 1, idxs, inputimages, inputdepthmaps, inp, device, stats, normalmap_wrap), None
+                launched, failure = _launch_group(gi & 1, idxs, inputimages, inputdepthmaps, inp, device, stats, normalmap_wrap,
+                                                  normalmap_bilateral), None
                 stats["launch"] = stats.get("launch", 0.0) + (_time.perf_counter() - _t0)
             except Exception as e:          # noqa: BLE001 -- re-raised below, after the results that precede it
                 launched, failure = None, e
