@@ -1,4 +1,4 @@
-/* TEST INFRASTRUCTURE.  The fused normal-map kernels (csrc/ds_normalmap.hip, nm_store) compute the three components of
+/* TEST INFRASTRUCTURE.  The fused normal-map kernels (csrc/ds_normalmap.hip, nm_pixel) compute the three components of
  *     normal = (zx, -zy, 1) / n,   n = sqrt(zx^2 + zy^2 + 1)                    normalmap_generation.py:34-39
  * with ONE correctly rounded division  y = 1.0 / n  (which is the z component) and, for the other two,
  *     q0 = a * y;  r = fma(-q0, n, a);  q = fma(r, y, q0)

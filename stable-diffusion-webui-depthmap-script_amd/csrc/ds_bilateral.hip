@@ -31,19 +31,6 @@
 #define BL_ROWS (BL_TH + 2 * BL_RMAX)
 #define BL_WR_LDS 2048              // leading entries of wr kept in LDS (16 KiB)
 
-__device__ __forceinline__ int bl_reflect101(int i, int n)
-{
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) { if (i < 0) i = -i; else i = 2 * (n - 1) - i; }
-    return i;
-}
-
-__device__ __forceinline__ int bl_mod(int i, int n)                  // i mod n in [0, n) for any i
-{
-    i %= n;
-    return i < 0 ? i + n : i;
-}
-
 template <int WRAP>
 __global__ __launch_bounds__(256) void k_bilateral_u16(const uint16_t *__restrict__ depth, int h, int w, int radius,
                                                        const double *__restrict__ ws, const double *__restrict__ wr,
@@ -58,8 +45,8 @@ __global__ __launch_bounds__(256) void k_bilateral_u16(const uint16_t *__restric
     const int pw = BL_TW + 2 * radius, ph = BL_TH + 2 * radius;          // the staged rectangle, pitch BL_PITCH
     for (int i = tid; i < pw * ph; i += 256) {
         const int ly = i / pw, lx = i - ly * pw;
-        const int gy = WRAP ? bl_mod(y0 + ly - radius, h) : bl_reflect101(y0 + ly - radius, h);
-        const int gx = WRAP ? bl_mod(x0 + lx - radius, w) : bl_reflect101(x0 + lx - radius, w);
+        const int gy = WRAP ? ds_mod(y0 + ly - radius, h) : ds_reflect101(y0 + ly - radius, h);
+        const int gx = WRAP ? ds_mod(x0 + lx - radius, w) : ds_reflect101(x0 + lx - radius, w);
         tile[ly * BL_PITCH + lx] = d[(size_t)gy * w + gx];
     }
     for (int i = tid; i < BL_WR_LDS; i += 256) wr_lds[i] = wr[i];

@@ -75,6 +75,22 @@ __device__ __forceinline__ uint8_t ds_f64_to_u8(double v)
     return (uint8_t)(long long)v;
 }
 
+// Image borders of the stencil kernels (ds_normalmap.hip, ds_bilateral.hip).
+// ds_reflect101: cv2's BORDER_REFLECT_101 (gfedcb|abcdefgh|gfedcba), any i; n == 1 gives 0.
+__device__ __forceinline__ int ds_reflect101(int i, int n)
+{
+    if (n == 1) return 0;
+    while (i < 0 || i >= n) { if (i < 0) i = -i; else i = 2 * (n - 1) - i; }
+    return i;
+}
+__device__ __forceinline__ int ds_mod(int i, int n)                  // i mod n in [0, n) for any i (a true modulo)
+{
+    i %= n;
+    return i < 0 ? i + n : i;
+}
+__device__ __forceinline__ int ds_wrap_prev(int i, int n) { return i > 0 ? i - 1 : n - 1; }      // (i - 1) mod n for i in [0, n)
+__device__ __forceinline__ int ds_wrap_next(int i, int n) { return i + 1 < n ? i + 1 : 0; }      // (i + 1) mod n for i in [0, n)
+
 __device__ __forceinline__ double ds_wave_min(double v)
 {
     for (int o = 32; o > 0; o >>= 1) { double t = __shfl_xor(v, o, 64); v = t < v ? t : v; }

@@ -271,31 +271,24 @@ def normalmap(depth, pre_blur, sobel_ksize, post_blur, invert, wrap=False):
     n, h, w = depth.shape
     assert depth.dtype in (torch.uint16, torch.float64, torch.float32, torch.float16) and depth.is_contiguous()
     out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=depth.device)
-    sfx = "_wrap" if wrap else ""
+    pre_blur, sobel_ksize, post_blur = int(pre_blur), int(sobel_ksize), int(post_blur)
+    # (entry point, its kernel-size arguments) by dtype
     if depth.dtype == torch.float16:
-        assert int(pre_blur) == 0 and int(post_blur) == 0 and int(sobel_ksize) == 0, "float16 depth: np.gradient without blurs only"
-        name = "ds_normalmap_gradient_f16" + sfx
-        CALLS[name] += 1
-        _check(getattr(lib(), name)(ctx_for(_dev_index(depth)), depth.data_ptr(), n, h, w, 1 if invert else 0,
-                                    out.data_ptr(), _stream(depth)))
-        return out
-    if depth.dtype == torch.float32:
-        assert int(sobel_ksize) == 0, "float32 depth: np.gradient only (cv2.Sobel is fed float64)"
-        if int(pre_blur) == 0 and int(post_blur) == 0:
-            name = "ds_normalmap_gradient_f32" + sfx
-            CALLS[name] += 1
-            _check(getattr(lib(), name)(ctx_for(_dev_index(depth)), depth.data_ptr(), n, h, w, 1 if invert else 0,
-                                        out.data_ptr(), _stream(depth)))
+        assert pre_blur == 0 and post_blur == 0 and sobel_ksize == 0, "float16 depth: np.gradient without blurs only"
+        name, sizes = "ds_normalmap_gradient_f16", ()
+    elif depth.dtype == torch.float32:
+        assert sobel_ksize == 0, "float32 depth: np.gradient only (cv2.Sobel is fed float64)"
+        if pre_blur == 0 and post_blur == 0:
+            name, sizes = "ds_normalmap_gradient_f32", ()
         else:
-            name = "ds_normalmap_gradient_blur_f32" + sfx
-            CALLS[name] += 1
-            _check(getattr(lib(), name)(ctx_for(_dev_index(depth)), depth.data_ptr(), n, h, w, int(pre_blur), int(post_blur),
-                                        1 if invert else 0, out.data_ptr(), _stream(depth)))
-        return out
-    name = ("ds_normalmap" if depth.dtype == torch.uint16 else "ds_normalmap_f64") + sfx
+            name, sizes = "ds_normalmap_gradient_blur_f32", (pre_blur, post_blur)
+    else:
+        name, sizes = ("ds_normalmap" if depth.dtype == torch.uint16 else "ds_normalmap_f64"), (pre_blur, sobel_ksize, post_blur)
+    if wrap:
+        name += "_wrap"
     CALLS[name] += 1
-    _check(getattr(lib(), name)(ctx_for(_dev_index(depth)), depth.data_ptr(), n, h, w, int(pre_blur), int(sobel_ksize),
-                                int(post_blur), 1 if invert else 0, out.data_ptr(), _stream(depth)))
+    _check(getattr(lib(), name)(ctx_for(_dev_index(depth)), depth.data_ptr(), n, h, w, *sizes, 1 if invert else 0,
+                                out.data_ptr(), _stream(depth)))
     return out
 
 

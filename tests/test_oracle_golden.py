@@ -151,7 +151,7 @@ def test_python_port_reproduces_reference_goldens(oracle):
 
 
 def _f16_kernel_model(depth, invert):
-    """k_nm_gradient_f16 (csrc/ds_normalmap.hip) written out in numpy float32 with an explicit rounding to half behind every
+    """k_nm_gradient_fused<_Float16, WRAP 0> (csrc/ds_normalmap.hip) written out in numpy float32 with an explicit rounding to half behind every
     operation -- the arithmetic the device kernel performs, operation by operation."""
     f, hf = np.float32, np.float16
 
