@@ -460,6 +460,26 @@ int ds_linear_vt(ds_ctx *ctx, const void *w_v, const void *h, void *vt, int64_t 
                  int64_t in_features, int dtype, void *stream);
 
 /*
+ * ds_linear_qkv -- the Q/K projection and V^T of one encoder block in ONE persistent GEMM launch:
+ *     qk = h . w_qk^T + b_qk   exactly as ds_linear(h, w_qk, b_qk, qk, batch * tokens, qk_features, in_features, qk_features, 0, ..)
+ *     vt                       exactly as ds_linear_vt(w_v, h, vt, v_channels, batch, tokens, in_features, ..)
+ * Both GEMMs read the same LayerNorm output and neither depends on the other: the persistent kernel walks the tile list of the first
+ * followed by the tile list of the second (operand bases, bias and store map switch per tile), so the two launches share their
+ * rounds -- at the benchmark 1032 + 516 tiles are six exact rounds of 256 plus 12 V^T tiles for one ragged launch, instead of
+ * 4 + 2 rounds and two ragged launches.  Every output element keeps its accumulation chain: both results are BIT-IDENTICAL to the
+ * two calls above (any DS_LIN_* setting but the K split, which does not apply here: every round of this route is one chain).
+ *   h [batch * tokens, in_features]   w_qk [qk_features, in_features]   b_qk [qk_features] or NULL   w_v [v_channels, in_features]
+ *   qk [batch * tokens, qk_features]  vt [batch, v_channels, tokens]
+ * The union of the two entry points' rules: tokens % 8 == 0, (batch * tokens) % 256 == 0, batch * tokens^2 < 2^32 (else
+ * DS_EUNSUPPORTED), qk_features % 256 == 0, v_channels >= 256, in_features % 128 == 0 (128 .. 16384), every pointer 16-byte aligned,
+ * dtype f16 or bf16; anything else DS_EINVAL.  Timers: the main launch runs under DS_KT_LINEAR, its ragged round under
+ * DS_KT_LINEAR + DS_KT_RAGGED (nothing is recorded under DS_KT_LINEAR_VT).  No counterpart in the reference (it runs one qkv Linear
+ * and permutes: dmidas/backbones/beit.py:71-74).
+ */
+int ds_linear_qkv(ds_ctx *ctx, const void *h, const void *w_qk, const void *b_qk, const void *w_v, void *qk, void *vt,
+                  int64_t batch, int64_t tokens, int64_t qk_features, int64_t v_channels, int64_t in_features, int dtype, void *stream);
+
+/*
  * ds_linear_shuffle -- ConvTranspose2d with kernel_size == stride as ONE GEMM with the pixel shuffle in the store address: the
  * 4x4-stride-4 and 2x2-stride-2 transposed convolutions of the reassemble stage (dmidas/backbones/utils.py:196-205 and :215-224,
  * `nn.ConvTranspose2d(features[i], features[i], kernel_size=4 / 2, stride=4 / 2, padding=0)`; ddepth_anything_v2/

@@ -2,7 +2,8 @@
 // instead of a library GEMM / convolution followed by element-wise passes.  Two front ends on one K loop:
 //   * dense:  the token GEMMs of the ViT encoders.  In the networks it runs `fc1 -> nn.GELU` of every encoder block (timm's
 //     Mlp as called from dmidas/backbones/beit.py:93-107; ddepth_anything_v2/depth_anything_v2/dinov2_layers/mlp.py:33-39),
-//     the Q/K projection, V^T (ds_linear_vt: written transposed by the epilogue), and the attention / MLP output projections
+//     the Q/K projection, V^T (ds_linear_vt: written transposed by the epilogue; ds_linear_qkv: both in one persistent launch over
+//     the two tile lists, VT 4 below), and the attention / MLP output projections
 //     with LayerScale + residual in the epilogue (ds_linear_residual).  Launches whose last round of tiles would be nearly
 //     empty hand those tiles to k_linear_ragged (below).
 //   * conv:   the 3x3 convolutions of the DPT decoders as an implicit GEMM with bias / ReLU / residual / skip in the epilogue
@@ -133,17 +134,38 @@ struct LinParams {
     // {rstd, -mean * rstd} and per output feature colsum = sum_k w[n][k] (of the rounded weights) complete the affine map in the epilogue
     const float2 *ln_stats;     // one pair per token: rows of x (VT: columns of the GEMM)
     const float *ln_colsum;     // one value per output feature: columns of y (VT: rows of the GEMM)
+    // VT 4 (two-segment tile list, ds_linear_qkv): positions [0, seg_t0) are the tiles of the dense GEMM described by the fields above
+    // (store of VT 0); positions seg_t0 .. are the tiles of a SECOND GEMM with the same K -- row operand x1 [M1, K], column operand w1
+    // (nbm1 x nbn1 tiles of 256 x 256), no bias, stored to y1 through the V^T map of VT 1 (vt_np / vt_c / vt_magic)
+    const void *x1, *w1;
+    void *y1;
+    int seg_t0, M1, nbm1, nbn1;
 };
+// The kernels take LinParams by value as their ONLY argument, so it sits at the start of the kernel-argument segment.  VT 4 reads the
+// fields of its second segment through this pointer, made opaque at every use: they are then fetched per tile (scalar loads of the
+// constant address space, counted by lgkmcnt, not vmcnt) instead of being kept in SGPRs across the K loop next to everything the
+// one-segment kernels already hold there -- that many live scalars spilled into VGPR lanes, and an accumulator into scratch.
+typedef const __attribute__((address_space(4))) LinParams *LinParamsK;
+__device__ __forceinline__ LinParamsK ln_kernarg()
+{
+    LinParamsK pk = (LinParamsK)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(pk));
+    return pk;
+}
 
 // position in the tile list -> origin of the tile.  The list is ordered in groups of 8 row panels, rows fastest inside a group
 // (see the kernel); the last row panel is shifted up to end at row M (M >= 256): its first rows are computed twice, identically
+__device__ __forceinline__ void ln_tile_origin(const int nbm, const int nbn, const int M, const int bnw, const int tile, int &bm0, int &bn0)
+{
+    const int grp8 = tile / (8 * nbn), rem8 = tile - grp8 * (8 * nbn);
+    const int rows8 = min(8, nbm - 8 * grp8);
+    const int bn = rem8 / rows8, bm = 8 * grp8 + (rem8 - bn * rows8);
+    bm0 = min(bm * 256, M - 256);
+    bn0 = bn * bnw;
+}
 __device__ __forceinline__ void ln_tile_origin(const LinParams &P, const int tile, int &bm0, int &bn0)
 {
-    const int grp8 = tile / (8 * P.nbn), rem8 = tile - grp8 * (8 * P.nbn);
-    const int rows8 = min(8, P.nbm - 8 * grp8);
-    const int bn = rem8 / rows8, bm = 8 * grp8 + (rem8 - bn * rows8);
-    bm0 = min(bm * 256, P.M - 256);
-    bn0 = bn * P.bnw;
+    ln_tile_origin(P.nbm, P.nbn, P.M, P.bnw, tile, bm0, bn0);
 }
 
 // element offset of output (row, col .. col + 7), col a multiple of 8.  VT: the GEMM computes W_v . h^T with the TOKENS as its
@@ -266,6 +288,13 @@ template <int N> __device__ __forceinline__ void ln_wait_vm() { asm volatile("s_
 // counted wait stay exactly as they are -- the B1 half-tile is still staged (with B0's source: a dummy that keeps the DMA
 // count per phase), only its fragment reads and the MFMAs of the two (.., B1) quadrants are gone, and the epilogue stores 8
 // pieces per tile instead of 16 (the early mode's store count follows).  Half the MFMAs for ~2/3 of the phase time.
+// VT = 4: ONE persistent walk over the concatenated tile lists of two GEMMs with a common K (LinParams: seg_t0 ..) -- the Q/K projection
+// (segment 0: geometry, tile order and store of VT 0) and V^T (segment 1: those of VT 1) of an encoder block, which read the same
+// LayerNorm output.  set_tile maps the position to a tile with the XCD-aware formula over the WHOLE list, then picks the segment
+// (workgroup-uniform: scalar work) and takes from it the tile geometry and the two operand bases; the bias pointer, the output base
+// and the store map follow the segment in the epilogue.  K loop, LDS map, DMA schedule and every counted wait are untouched: a tile of
+// either segment issues NBIAS bias loads (segment 1: the null-bias dummy) and 16 stores.  An output element keeps its accumulation
+// chain, so both results are bit-identical to the two separate launches.
 template <int BF16, int EPI, int CONV, int RES, int VT = 0, int NH = 0>
 __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
 {
@@ -304,7 +333,9 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
     // ---- the workgroup is persistent: it walks tiles orig = blockIdx.x, + gridDim.x, ... of the XCD-aware tile list (XCD x
     // takes tiles [start(x), start(x+1)) of the column-fastest list; gridDim.x is a multiple of 8, so a workgroup stays on
     // its XCD's range).  Per tile: origin, operand bases and (CONV) the border bits of this thread's four pixels.
+    static_assert(VT != 4 || (EPI == 0 && CONV == 0 && RES == 0 && NH == 0), "the two-segment tile list is built for the plain dense epilogue");
     int bm0 = 0, bn0 = 0;
+    int seg = 0;            // VT 4: the segment of the tile list the current tile belongs to (workgroup-uniform)
     const unsigned char *xb = nullptr, *wb = nullptr;
     unsigned okA = 0;       // CONV: bit 6*(2h+i) + t (t = 0..2): row y-1+t of this piece's pixel is inside the image; + 3 + t: column x-1+t
     auto set_tile = [&](const int orig) {
@@ -314,6 +345,17 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
         // are then 8 row panels x 4 column panels (12 operand panels per K-slice through that L2 instead of the 18 of a
         // column-fastest list)
         // (measured against chunks of 4 column panels outermost, which would keep W in L2: fc1 316-319 vs 328-331 us)
+        if constexpr (VT == 4) {
+            const LinParamsK pk = ln_kernarg();
+            const int t0 = pk->seg_t0;
+            seg = tile >= t0 ? 1 : 0;
+            if (seg) {          // the per-tile operand swap: segment 1 has its own geometry and operand bases (K and rowbytes are common)
+                ln_tile_origin(pk->nbm1, pk->nbn1, pk->M1, 256, tile - t0, bm0, bn0);
+                xb = (const unsigned char *)pk->x1 + (size_t)bm0 * rowbytes;
+                wb = (const unsigned char *)pk->w1 + (size_t)bn0 * K * sizeof(T);
+                return;
+            }
+        }
         ln_tile_origin(P, tile, bm0, bn0);
         xb = (const unsigned char *)P.x + (size_t)bm0 * rowbytes;
         wb = (const unsigned char *)P.w + (size_t)bn0 * K * sizeof(T);
@@ -386,9 +428,11 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
     // loaded BEFORE the last iteration of a tile (in flight under its MFMAs).  Always exactly NBIAS loads -- a null bias reads 16
     // valid bytes of W instead and is zeroed afterwards -- because the last iteration's counted waits include them.  (The
     // LayerScale vector of EPI 3 is loaded in the epilogue next to the residuals: that variant waits there anyway.)
+    // VT 4: the decision is per tile -- segment 1 has no bias.  Both macros run while `seg` is still the CURRENT tile's.
+#define LN_NULL_BIAS() (!P.bias || (VT == 4 && seg))
 #define LN_LOAD_BIAS()                                                                                                   \
     do {                                                                                                                 \
-        const T *bias_ = (const T *)P.bias;                                                                              \
+        const T *bias_ = LN_NULL_BIAS() ? (const T *)nullptr : (const T *)P.bias;                                        \
         _Pragma("unroll") for (int hb_ = 0; hb_ < 2; ++hb_) _Pragma("unroll") for (int k_ = 0; k_ < NBK; ++k_) {         \
             const int c_ = bn0 + (NH ? wc * 32 : wc * 64 + hb_ * 32) + c8 + 16 * k_;                                     \
             bv[hb_][k_] = *(const V8 *)(bias_ ? bias_ + c_ : (const T *)P.w);                                            \
@@ -396,7 +440,7 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
     } while (0)
 #define LN_ZERO_NULL_BIAS()                                                                                              \
     do {                                                                                                                 \
-        if (!P.bias) {                                                                                                   \
+        if (LN_NULL_BIAS()) {                                                                                            \
             _Pragma("unroll") for (int hb_ = 0; hb_ < 2; ++hb_) _Pragma("unroll") for (int k_ = 0; k_ < NBK; ++k_)       \
                 _Pragma("unroll") for (int t_ = 0; t_ < 8; ++t_) bv[hb_][k_][t_] = (T)0.f;                               \
         }                                                                                                                \
@@ -610,11 +654,37 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
         if (wr == 0) LN_BARRIER();                         // wave-row 0 arrives at wave-row 1's last barrier
     }
     // every fragment read of this tile was retired before that barrier: LDS is free for the next tile's prologue
+    // (early mode runs set_tile(next) BEFORE the epilogue: everything the epilogue reads per tile is captured here -- the origin, and for
+    // VT 4 the segment, which decides the output base and the store map; the null-bias decision is taken right here)
     const int cbm0 = bm0, cbn0 = bn0;
+    const bool cseg = VT == 4 && seg != 0;
     const int next = orig + (int)gridDim.x;
-    const int hi8 = 8 * (lane >> 5);
+    // (VT 4: the lane index the epilogue forms its rows and columns from is made opaque HERE, per tile.  With two store maps the
+    // loop-invariant per-lane address parts of BOTH would otherwise be hoisted out of the tile loop and kept in registers across the
+    // K loop, which has none to spare: an accumulator spilled, and its reload put a vmcnt(0) into the MFMA part of a phase.  Formed
+    // per tile they cost a few VALU operations in the epilogue, where the fragment registers are free.)
+    int elane = lane;
+    if constexpr (VT == 4) asm volatile("" : "+v"(elane));
+    const int hi8 = 8 * (elane >> 5);
+    const int ec8 = MF16 ? 16 * ((elane >> 4) & 1) + 8 * (elane >> 5) : 8 * (elane >> 5);       // c8 of the epilogue
     LN_ZERO_NULL_BIAS();
     T *yb = (T *)P.y;
+    unsigned s1_np = 0, s1_c = 0, s1_magic = 0;                 // VT 4, a tile of segment 1: the V^T store map (ln_out_off<1>)
+    if constexpr (VT == 4) {
+        if (cseg) {
+            const LinParamsK pk = ln_kernarg();
+            yb = (T *)pk->y1;
+            s1_np = (unsigned)pk->vt_np; s1_c = (unsigned)pk->vt_c; s1_magic = pk->vt_magic;
+        }
+    }
+    // element offset of the 8 outputs (row, col .. col + 7) of this tile; o0 = their offset in a row-major y
+    auto tile_out_off = [&](const int row, const int col, const size_t o0) -> size_t {
+        if constexpr (VT == 4) {
+            if (!cseg) return o0;
+            const unsigned b = __umulhi((unsigned)col, s1_magic), n = (unsigned)col - b * s1_np;
+            return ((size_t)b * s1_c + row) * (size_t)s1_np + n;
+        } else return VT ? ln_out_off<VT>(P, row, col) : o0;
+    };
     // (CONV 3 / 4: the base stays a scalar HERE, so that the per-lane store address is formed per tile instead of being hoisted out
     // of the tile loop and spilled -- the circular gather has no register to spare, and a reload in the epilogue would be a
     // vmcnt(0) behind the next tile's prologue DMAs)
@@ -644,7 +714,7 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
         V8 gv[2];                                                   // EPI 3: the per-column LayerScale factors, packed like the bias
         if (EPI == 3) {
 #pragma unroll
-            for (int hb = 0; hb < 2; ++hb) gv[hb] = *(const V8 *)((const T *)P.gamma + cbn0 + (NH ? wc * 32 : wc * 64 + hb * 32) + c8);
+            for (int hb = 0; hb < 2; ++hb) gv[hb] = *(const V8 *)((const T *)P.gamma + cbn0 + (NH ? wc * 32 : wc * 64 + hb * 32) + ec8);
         }
         constexpr int NHB = NH ? 1 : 2;                             // W halves with results (NH: the B0 half alone)
         const int wcol = NH ? wc * 32 : wc * 64;
@@ -652,8 +722,8 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
         for (int ha = 0; ha < 2; ++ha)
 #pragma unroll
             for (int rb = 0; rb < 4; ++rb) {
-                const int row = cbm0 + wr * 128 + ha * 64 + rb * 16 + (lane & 15);
-                const int col = cbn0 + wcol + c8;                   // + 32 hb
+                const int row = cbm0 + wr * 128 + ha * 64 + rb * 16 + (elane & 15);
+                const int col = cbn0 + wcol + ec8;                  // + 32 hb
                 const size_t o0 = (size_t)row * P.ldy + col;
                 V8 ra[2], rb2[2];                                    // residual pieces [W half]
                 constexpr bool LNF = EPI == 4 || EPI == 5;
@@ -705,7 +775,7 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
                         o[t] = (T)u[0];
                         o[t + 1] = (T)u[1];
                     }
-                    T *dst = yb + (VT ? ln_out_off<VT>(P, row, col + hb * 32) : o0 + hb * 32);
+                    T *dst = yb + tile_out_off(row, col + hb * 32, o0 + hb * 32);
                     if (!LN_ABLATE(1)) *(V8 *)dst = o;
                     else asm volatile("" ::"v"(o));
                 }
@@ -732,11 +802,11 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
         for (int ha = 0; ha < 2; ++ha)
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb) {
-                const int rl = ha * 64 + rb * 32 + (lane & 31);     // row inside the wave tile
+                const int rl = ha * 64 + rb * 32 + (elane & 31);    // row inside the wave tile
                 const size_t o0 = (size_t)(cbm0 + wr * 128 + rl) * P.ldy + cbn0 + wcol + hi8;
                 // VT: where the 8 columns of piece (hb, k) go (per batch element [channels][tokens]); else o0 + hb * 32 + 16 * k
                 auto out_off = [&](const int hb_, const int k_) -> size_t {
-                    return VT ? ln_out_off<VT>(P, cbm0 + wr * 128 + rl, cbn0 + wcol + hi8 + hb_ * 32 + 16 * k_) : o0 + hb_ * 32 + 16 * k_;
+                    return tile_out_off(cbm0 + wr * 128 + rl, cbn0 + wcol + hi8 + hb_ * 32 + 16 * k_, o0 + hb_ * 32 + 16 * k_);
                 };
                 V8 ra[2][2], rb2[2][2];                              // residual pieces [W half][k]
                 constexpr bool LNF = EPI == 4 || EPI == 5;
@@ -1468,6 +1538,63 @@ static int ln_launch(ds_ctx *ctx, const LinParams &P0, hipStream_t stream)
     return DS_OK;
 }
 
+// The Q/K projection and V^T of an encoder block as ONE persistent walk (k_linear256<.., VT 4>).  PQ describes the dense GEMM, PV the
+// V^T GEMM as ds_linear_vt sets it up; the walked list is PQ's T0 tiles followed by PV's T1.  The ragged rule applies to T0 + T1: the
+// R left-over tiles are the tail of the list, i.e. V^T tiles, and go to the V^T instantiations of k_linear_ragged with PV alone and
+// n_main = T1 - R (one accumulation chain over the whole of K, like every round since round 6: no K split on this route).  R > T1, or
+// ragged rounds off: the persistent kernel walks everything.  k_linear_thin is never launched here -- Q/K's last row panel sits inside
+// the main rounds.
+template <int BF16>
+static int ln_launch_qkv(ds_ctx *ctx, const LinParams &PQ, const LinParams &PV0, hipStream_t stream)
+{
+    static std::atomic<uint64_t> attr_done{0};
+    auto fn = k_linear256<BF16, 0, 0, 0, 4>;
+    DS_HIP_CHECK(hipSetDevice(ctx->device));
+    const uint64_t bit = 1ull << (ctx->device & 63);
+    if (!(attr_done.load(std::memory_order_relaxed) & bit)) {
+        DS_HIP_CHECK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, LN_LDS_BYTES));
+        DS_HIP_CHECK(hipFuncSetAttribute((const void *)k_linear_ragged<BF16, 0, 0, 1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * RG_SLOT));
+        DS_HIP_CHECK(hipFuncSetAttribute((const void *)k_linear_ragged<BF16, 0, 0, 1, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 6 * RG_SLOT));
+        DS_HIP_CHECK(hipFuncSetAttribute((const void *)k_linear_ragged<BF16, 0, 0, 1, 6, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 6 * RG_SLOT));
+        attr_done.fetch_or(bit, std::memory_order_relaxed);
+    }
+    if (!ctx->ncu) {
+        int ncu = 0;
+        DS_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+        ctx->ncu = ncu >= 8 ? ncu / 8 * 8 : 8;
+    }
+    const LinOptions &O = ln_options();
+    int grid = ctx->ncu;
+    if (O.grid >= 8) grid = O.grid / 8 * 8;
+    const int t0 = PQ.nbm * PQ.nbn, t1 = PV0.nbm * PV0.nbn, ntiles = t0 + t1;
+    int ragged = 0;
+    if (ntiles > grid) {
+        const int r = ntiles % grid;
+        if (O.ragged && r > 0 && O.ragged_den > 0 && O.ragged_den * r <= grid && r <= t1) ragged = r;
+    }
+    LinParams P = PQ, PV = PV0;
+    P.bnw = PV.bnw = 256;
+    P.early = O.early;
+    P.x1 = PV.x; P.w1 = PV.w; P.y1 = PV.y;
+    P.seg_t0 = t0; P.M1 = PV.M; P.nbm1 = PV.nbm; P.nbn1 = PV.nbn;
+    P.vt_np = PV.vt_np; P.vt_c = PV.vt_c; P.vt_magic = PV.vt_magic;
+    P.n_main = ntiles - ragged;
+    PV.n_main = t1 - ragged;
+    const int kt0 = ds_kt_begin(ctx, DS_KT_LINEAR, stream);
+    hipLaunchKernelGGL(fn, dim3(P.n_main < grid ? P.n_main : grid), dim3(LN_THREADS), LN_LDS_BYTES, stream, P);
+    ds_kt_end(ctx, DS_KT_LINEAR, kt0, stream);
+    if (ragged) {
+        const int deep = O.ragged_ring ? O.ragged_ring == 6 : 8 * ragged <= grid;
+        const int kt1 = ds_kt_begin(ctx, DS_KT_LINEAR + DS_KT_RAGGED, stream);
+        if (deep && O.ragged_pipe) hipLaunchKernelGGL((k_linear_ragged<BF16, 0, 0, 1, 6, 1>), dim3(8 * ragged), dim3(LN_THREADS), 6 * RG_SLOT, stream, PV);
+        else if (deep) hipLaunchKernelGGL((k_linear_ragged<BF16, 0, 0, 1, 6>), dim3(8 * ragged), dim3(LN_THREADS), 6 * RG_SLOT, stream, PV);
+        else hipLaunchKernelGGL((k_linear_ragged<BF16, 0, 0, 1, 3>), dim3(8 * ragged), dim3(LN_THREADS), 3 * RG_SLOT, stream, PV);
+        ds_kt_end(ctx, DS_KT_LINEAR + DS_KT_RAGGED, kt1, stream);
+    }
+    DS_HIP_CHECK(hipGetLastError());
+    return DS_OK;
+}
+
 template <int BF16>
 static int ln_dispatch_dense(ds_ctx *ctx, const LinParams &P, int act, hipStream_t st)
 {
@@ -1640,6 +1767,46 @@ DS_API int ds_linear_vt(ds_ctx *ctx, const void *w_v, const void *h, void *vt, i
     P.kt_kind = DS_KT_LINEAR_VT;
     hipStream_t st = (hipStream_t)stream;
     return dtype == DS_DTYPE_F16 ? ln_launch<0, 0, 0, 0, 1>(ctx, P, st) : ln_launch<1, 0, 0, 0, 1>(ctx, P, st);
+}
+
+// The Q/K projection and V^T of an encoder block in one persistent launch: qk = h . W_qk^T + b_qk exactly as ds_linear computes it
+// (act 0, ldy = qk_features) and vt exactly as ds_linear_vt does -- both read the same LayerNorm output h, and neither depends on the
+// other.  Two main kernels, the thin round of Q/K's last row panel and V^T's own ragged round become one walk over both tile lists
+// plus at most one ragged launch (ln_launch_qkv).  The argument checks are the union of the two entry points'.
+DS_API int ds_linear_qkv(ds_ctx *ctx, const void *h, const void *w_qk, const void *b_qk, const void *w_v, void *qk, void *vt,
+                         int64_t batch, int64_t tokens, int64_t qk_features, int64_t v_channels, int64_t in_features, int dtype, void *stream)
+{
+    DS_REQUIRE(ctx && h && w_qk && w_v && qk && vt, DS_EINVAL, "ds_linear_qkv: null argument");
+    DS_REQUIRE(batch > 0 && tokens > 0 && tokens % 8 == 0 && (batch * tokens) % 256 == 0 && batch * tokens < (1ll << 31) - 256, DS_EINVAL,
+               "ds_linear_qkv: tokens must be a multiple of 8 and batch * tokens a multiple of 256");
+    DS_REQUIRE(batch * tokens * tokens < (1ll << 32), DS_EUNSUPPORTED, "ds_linear_qkv: batch * tokens^2 must stay below 2^32");
+    DS_REQUIRE(qk_features > 0 && qk_features % 256 == 0, DS_EINVAL, "ds_linear_qkv: qk_features must be a multiple of 256");
+    DS_REQUIRE(v_channels >= 256 && v_channels < (1ll << 31) - 256, DS_EINVAL, "ds_linear_qkv: v_channels must be >= 256 (one tile)");
+    DS_REQUIRE(in_features >= 128 && in_features % 128 == 0 && in_features <= 16384, DS_EINVAL,
+               "ds_linear_qkv: in_features must be a multiple of 128 (<= 16384)");
+    DS_REQUIRE((batch * tokens / 256) * (qk_features / 256) + ((v_channels + 255) / 256) * (batch * tokens / 256) < (1ll << 31), DS_EINVAL,
+               "ds_linear_qkv: too many tiles");
+    DS_REQUIRE(dtype == DS_DTYPE_F16 || dtype == DS_DTYPE_BF16, DS_EINVAL, "ds_linear_qkv: dtype must be f16 or bf16");
+    DS_REQUIRE(((uintptr_t)h & 15) == 0 && ((uintptr_t)w_qk & 15) == 0 && ((uintptr_t)w_v & 15) == 0 && ((uintptr_t)qk & 15) == 0 &&
+               ((uintptr_t)vt & 15) == 0 && (!b_qk || ((uintptr_t)b_qk & 15) == 0), DS_EINVAL,
+               "ds_linear_qkv: h, w_qk, w_v (the LDS-DMA sources), qk, vt and b_qk must be 16-byte aligned");
+    const int64_t rows = batch * tokens;
+    LinParams PQ, PV;
+    memset(&PQ, 0, sizeof(PQ));
+    memset(&PV, 0, sizeof(PV));
+    PQ.x = h; PQ.w = w_qk; PQ.bias = b_qk; PQ.y = qk;
+    PQ.M = (int)rows; PQ.N = (int)qk_features; PQ.K = (int)in_features;
+    PQ.nbm = (int)(rows / 256); PQ.nbn = (int)(qk_features / 256);
+    PQ.ldy = qk_features;
+    PQ.kt_kind = DS_KT_LINEAR;
+    PV.x = w_v; PV.w = h; PV.y = vt;
+    PV.M = (int)v_channels; PV.N = (int)rows; PV.K = (int)in_features;
+    PV.nbm = (int)((v_channels + 255) / 256); PV.nbn = (int)(rows / 256);
+    PV.ldy = rows;
+    PV.vt_np = (int)tokens; PV.vt_c = (int)v_channels; PV.vt_magic = (unsigned)((1ull << 32) / (unsigned long long)tokens + 1ull);
+    PV.kt_kind = DS_KT_LINEAR;
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == DS_DTYPE_F16 ? ln_launch_qkv<0>(ctx, PQ, PV, st) : ln_launch_qkv<1>(ctx, PQ, PV, st);
 }
 
 // ConvTranspose2d with kernel_size == stride (no overlap between the taps of neighbouring pixels) is a plain GEMM whose output

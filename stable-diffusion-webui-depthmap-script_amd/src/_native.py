@@ -20,7 +20,7 @@ DS_DEPTH_U16, DS_DEPTH_F32, DS_DEPTH_F64 = 0, 1, 2
 FILL_IDS = {"none": 0, "naive": 1, "naive_interpolating": 2, "polylines_soft": 3, "polylines_sharp": 4}
 
 EXPORTS = [
-    "ds_version", "ds_last_error", "ds_normalmap_f64", "ds_normalmap_gradient_f32", "ds_reassemble_readout", "ds_bias_act_nhwc", "ds_linear", "ds_linear_residual", "ds_linear_vt", "ds_conv3x3_nhwc", "ds_ctx_create", "ds_ctx_destroy", "ds_stereo_warp", "ds_depth_minmax",
+    "ds_version", "ds_last_error", "ds_normalmap_f64", "ds_normalmap_gradient_f32", "ds_reassemble_readout", "ds_bias_act_nhwc", "ds_linear", "ds_linear_residual", "ds_linear_vt", "ds_linear_qkv", "ds_conv3x3_nhwc", "ds_ctx_create", "ds_ctx_destroy", "ds_stereo_warp", "ds_depth_minmax",
     "ds_stereo_last_exact_rows", "ds_copy_view", "ds_overlap_red_cyan", "ds_normalmap", "ds_depth_to_u16",
     "ds_convert_to_i16", "ds_profile_enable", "ds_profile_last_ms", "ds_stereo_last_stats", "ds_attention_fwd", "ds_attention_bias_pack", "ds_colorize_u16", "ds_residual_layernorm", "ds_boost_blend", "ds_upsample_bilinear_nhwc", "ds_dpt_head_tail", "ds_preprocess_bicubic", "ds_linear_reload_env", "ds_attention_reload_env", "ds_normalmap_selfcheck", "ds_normalmap_gradient_f16", "ds_normalmap_gradient_blur_f32",
     "ds_linear_shuffle", "ds_linear_readout", "ds_kernel_timer_enable", "ds_kernel_timer_read", "ds_kernel_timer_read_each", "ds_group_norm_nchw",
@@ -45,6 +45,8 @@ _lib_lock = threading.Lock()
 
 # How often each C-ABI entry point was reached through this binding (tests and bench.py's route_check assert that a forward
 # really took the in-tree kernels it claims: a routing threshold that silently sends a shape to the library shows up here).
+# ds_linear_qkv runs two of the counted GEMMs in one launch: it counts under its own name AND once under ds_linear and ds_linear_vt,
+# so "how many Q/K and V^T GEMMs ran in-tree" reads the same on either route; ds_linear_qkv alone tells the routes apart.
 CALLS = collections.Counter()
 
 
@@ -96,6 +98,7 @@ def lib():
             L.ds_linear.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, ci, ci, vp]
             L.ds_linear_residual.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, ci, vp]
             L.ds_linear_vt.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, ci, vp]
+            L.ds_linear_qkv.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, vp]
             L.ds_conv3x3_nhwc.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
             L.ds_conv3x3_nhwc_circular.argtypes = L.ds_conv3x3_nhwc.argtypes
             L.ds_linear_shuffle.argtypes = [vp, vp, vp, vp, vp, i64, i64, ci, ci, ci, ci, vp]
@@ -936,6 +939,43 @@ def linear_vt(w_v, h):
     _check(lib().ds_linear_vt(ctx_for(_dev_index(h)), w.data_ptr(), h2.data_ptr(), out.data_ptr(), c, b, npad, k,
                               1 if h.dtype == torch.float16 else 2, _stream(h)))
     return out
+
+
+def linear_qkv_supported(h, w_qk, w_v):
+    """Shapes ds_linear_qkv takes: those of linear (h, w_qk) and of linear_vt (w_v, h) at once."""
+    return linear_vt_supported(w_v, h) and linear_supported(h, w_qk) and w_qk.shape[1] == h.shape[2]
+
+
+def linear_qkv(h, w_qk, b_qk, w_v, out=None):
+    """(h @ w_qk.T + b_qk, V^T = W_v . h^T per batch element) in ONE persistent GEMM launch (include/depthstereo.h: ds_linear_qkv),
+    bit-identical to (linear(h, w_qk, b_qk), linear_vt(w_v, h)).  h [B, Np, K] float16 / bfloat16 CUDA, w_qk [N, K], b_qk [N] or
+    None, w_v [C, K] -> (qk [B, Np, N], vt [B, C, Np]).  out: an optional (qk, vt) pair of contiguous tensors to write into.
+    CALLS counts the entry point, and the two GEMMs it carries as the kinds they are (ds_linear, ds_linear_vt)."""
+    torch = require_gpu()
+    assert h.is_cuda and h.dtype in (torch.float16, torch.bfloat16) and linear_qkv_supported(h, w_qk, w_v)
+    b, npad, k = h.shape
+    n, c = w_qk.shape[0], w_v.shape[0]
+    h2 = h if h.is_contiguous() else h.contiguous()
+
+    def prep(t):
+        if t is None:
+            return None
+        t = t.detach()
+        return t if (t.dtype == h.dtype and t.is_contiguous()) else t.to(h.dtype).contiguous()
+    wq, bq, wv = prep(w_qk), prep(b_qk), prep(w_v)
+    if out is None:
+        qk = torch.empty((b, npad, n), dtype=h.dtype, device=h.device)
+        vt = torch.empty((b, c, npad), dtype=h.dtype, device=h.device)
+    else:
+        qk, vt = out
+        assert tuple(qk.shape) == (b, npad, n) and tuple(vt.shape) == (b, c, npad) and qk.is_contiguous() and vt.is_contiguous()
+        assert qk.dtype == vt.dtype == h.dtype and qk.device == vt.device == h.device
+    CALLS["ds_linear_qkv"] += 1
+    CALLS["ds_linear"] += 1
+    CALLS["ds_linear_vt"] += 1
+    _check(lib().ds_linear_qkv(ctx_for(_dev_index(h)), h2.data_ptr(), wq.data_ptr(), None if bq is None else bq.data_ptr(), wv.data_ptr(),
+                               qk.data_ptr(), vt.data_ptr(), b, npad, n, c, k, 1 if h.dtype == torch.float16 else 2, _stream(h)))
+    return qk, vt
 
 
 def conv3x3_supported(conv, x):

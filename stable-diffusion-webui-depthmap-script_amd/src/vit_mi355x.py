@@ -184,6 +184,20 @@ def hip_gemm_ok(rows, out_features):
     return rows >= 256 and ((rows + 255) // 256) * (out_features // 256) >= LINEAR_HIP_MIN_TILES
 
 
+# The Q/K projection and V^T of a block as ONE persistent launch (ds_linear_qkv: the two tile lists walked back to back, bit-identical
+# results) wherever BOTH GEMMs would take the in-tree kernel on their own; "0" keeps the two launches (A/B runs).  The LayerNorm-fold
+# route has its own entry points and is not affected.
+LINEAR_QKV = os.environ.get("DS_LINEAR_QKV", "1") != "0"
+
+
+def linear_qkv_ok(h, w_qk, w_v):
+    if not (LINEAR_QKV and LINEAR_HIP == "all" and half_on_gpu(h) and h.dim() == 3):
+        return False
+    from . import _native
+    rows = h.shape[0] * h.shape[1]
+    return (_native.linear_qkv_supported(h, w_qk, w_v) and hip_gemm_ok(rows, w_qk.shape[0]) and hip_gemm_ok(w_v.shape[0], rows))
+
+
 # Every "half precision on the GPU -> in-tree kernel" decision of the networks goes through this predicate, so that ONE switch
 # (stock_routing below) turns the same network into its stock-torch twin: aten LayerNorm / softmax / GELU / interpolate and library
 # GEMMs / convolutions in half, i.e. the arithmetic the reference itself runs on a GPU in half precision.
@@ -332,8 +346,13 @@ class EncoderBlock(nn.Module):
         """LayerNorm-ed tokens -> (attention output before the projection, V bias to fold into the projection bias)."""
         b, npad, c = h.shape
         w_qk, b_qk, w_v, b_v = self.qkv_weights()
-        qk = linear(h, w_qk, b_qk).view(b, npad, 2, self.num_heads, HEAD_DIM)
-        vt = v_transposed(w_v, h)                               # [B, C, Np]: V transposed, straight out of the GEMM
+        if linear_qkv_ok(h, w_qk, w_v):                         # both GEMMs in one persistent launch, same bits
+            from . import _native
+            qk, vt = _native.linear_qkv(h, w_qk, b_qk, w_v)
+            qk = qk.view(b, npad, 2, self.num_heads, HEAD_DIM)
+        else:
+            qk = linear(h, w_qk, b_qk).view(b, npad, 2, self.num_heads, HEAD_DIM)
+            vt = v_transposed(w_v, h)                           # [B, C, Np]: V transposed, straight out of the GEMM
         return fused_attention(qk, vt, n_valid, self.scale, self.attention_bias(npad, grid_hw, h.dtype, h.device)), b_v
 
     def attend(self, h, n_valid, grid_hw):
