@@ -671,6 +671,47 @@ int ds_boost_blend(ds_ctx *ctx, float *dst, int64_t dst_row_stride, int height, 
                    int n_patches, const float *preds, int pred_size, const float *mask_template, int mask_size,
                    void *stream);
 
+/*
+ * The two ends of a DPT forward (csrc/ds_forward_ends.hip).  Each entry point below replaces a chain of copy / conversion passes
+ * and leaves the same bits; none allocates or synchronises; all are asynchronous on `stream`.
+ *
+ * ds_preprocess_bicubic_rows -- ds_preprocess_bicubic, storing the operand of the patch-embedding GEMM instead of the NHWC network
+ * input.  With gh = out_h / patch, gw = out_w / patch:
+ *   rows [batch, n_pad, kpad] (f16 / bf16, 16-byte aligned):
+ *     rows[b][1 + gy * gw + gx][(py * patch + px) * 3 + c] = ds_preprocess_bicubic's out[b][c][gy * patch + py][gx * patch + px]
+ *     row 0, rows 1 + gh * gw .. n_pad - 1 and columns 3 * patch^2 .. kpad - 1 are zero (written here: no fill needed);
+ *     output pixels beyond gh * patch x gw * patch are not computed.
+ *   patch 1..32, kpad % 8 == 0, kpad >= 3 * patch^2, n_pad >= 1 + gh * gw.  Any input / output size and row pitch; source bytes
+ *   come in through LDS in aligned 16-byte pieces, horizontal sums are shared by the output rows that tap the same source row.
+ *   Per output element the operation order, and so the value, is ds_preprocess_bicubic's.
+ */
+int ds_preprocess_bicubic_rows(ds_ctx *ctx, const void *images, void *rows, int batch, int in_h, int in_w, int out_h, int out_w,
+                               int flip_channels, const float *mean, const float *std, int patch, int n_pad, int kpad, int dtype,
+                               void *stream);
+
+/*
+ * ds_tokens_fixup -- tokens [batch, n_pad, channels] (f16 / bf16): row 0 of every image <- cls [channels], rows n_valid .. n_pad - 1
+ * <- 0.  After ds_linear on the rows above this is pad_tokens(cat(cls, patch_embed(x))).  channels % 8 == 0, 16-byte alignment.
+ */
+int ds_tokens_fixup(ds_ctx *ctx, void *tokens, const void *cls, int batch, int n_pad, int n_valid, int channels, int dtype, void *stream);
+
+/*
+ * ds_upsample_bicubic_to_f32 -- in [batch, in_h, in_w] (f16 / bf16) -> out float32 [batch, out_h, out_w]:
+ * F.interpolate(in[:, None], (out_h, out_w), mode="bicubic", align_corners=False)[:, 0].float() in one pass, bit for bit: cubic
+ * convolution (A = -0.75) on half-pixel centres, replicated border, float32 accumulation in torch's operation order, one rounding
+ * to the input type, widened (src/depthmap_generation.py:484-489 + the .float() of the callers).
+ */
+int ds_upsample_bicubic_to_f32(ds_ctx *ctx, const void *in, void *out, int batch, int in_h, int in_w, int out_h, int out_w, int dtype,
+                               void *stream);
+
+/*
+ * ds_im2col3x3_s2_nhwc -- x [batch, height, width, channels] (f16 / bf16) -> rows [batch * ho * wo, 9 * channels], ho = (height - 1) / 2 + 1,
+ * wo likewise: rows[(b, oy, ox)][(ky, kx, c)] = x[b][2 * oy + ky - 1][2 * ox + kx - 1][c], outside the map 0 (circular: the pixel
+ * on the opposite side, F.pad(mode="circular")) -- the GEMM operand of a 3x3 / stride 2 / padding 1 convolution.  channels % 8 == 0.
+ */
+int ds_im2col3x3_s2_nhwc(ds_ctx *ctx, const void *x, void *rows, int batch, int height, int width, int channels, int circular, int dtype,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,18 @@ __device__ __forceinline__ int ds_mod(int i, int n)                  // i mod n 
 __device__ __forceinline__ int ds_wrap_prev(int i, int n) { return i > 0 ? i - 1 : n - 1; }      // (i - 1) mod n for i in [0, n)
 __device__ __forceinline__ int ds_wrap_next(int i, int n) { return i + 1 < n ? i + 1 : 0; }      // (i + 1) mod n for i in [0, n)
 
+// The four taps of the cubic convolution kernel (A = -0.75) at fraction t, as ds_preprocess_bicubic and
+// ds_preprocess_bicubic_rows evaluate them (one statement: the two kernels must give the same bits).
+__device__ __forceinline__ void pre_cubic(float t, float *c)
+{
+    const float A = -0.75f;
+    const float x0 = t + 1.0f, x3 = 2.0f - t, x2 = 1.0f - t;
+    c[0] = ((A * x0 - 5.0f * A) * x0 + 8.0f * A) * x0 - 4.0f * A;
+    c[1] = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;
+    c[2] = ((A + 2.0f) * x2 - (A + 3.0f)) * x2 * x2 + 1.0f;
+    c[3] = ((A * x3 - 5.0f * A) * x3 + 8.0f * A) * x3 - 4.0f * A;
+}
+
 __device__ __forceinline__ double ds_wave_min(double v)
 {
     for (int o = 32; o > 0; o >>= 1) { double t = __shfl_xor(v, o, 64); v = t < v ? t : v; }

@@ -272,16 +272,6 @@ struct PreParams {
     long long total;
 };
 
-__device__ __forceinline__ void pre_cubic(float t, float *c)
-{
-    const float A = -0.75f;
-    const float x0 = t + 1.0f, x3 = 2.0f - t, x2 = 1.0f - t;
-    c[0] = ((A * x0 - 5.0f * A) * x0 + 8.0f * A) * x0 - 4.0f * A;
-    c[1] = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;
-    c[2] = ((A + 2.0f) * x2 - (A + 3.0f)) * x2 * x2 + 1.0f;
-    c[3] = ((A * x3 - 5.0f * A) * x3 + 8.0f * A) * x3 - 4.0f * A;
-}
-
 template <int DT>      // 0 f16, 1 bf16, 2 f32
 __global__ __launch_bounds__(256) void k_preprocess_bicubic(PreParams P)
 {

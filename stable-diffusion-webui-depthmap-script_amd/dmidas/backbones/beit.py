@@ -217,6 +217,14 @@ class Beit(nn.Module):
         _, taps = vm.run_blocks(self.blocks, t, n_valid, grid, set(hooks), padded_taps=padded)
         return [taps[i] for i in hooks], grid, n_valid
 
+    def forward_taps_rows(self, rows, grid, hooks, padded=False):
+        """forward_taps from the padded patch rows of the image (ds_preprocess_bicubic_rows: [B, n_pad, kpad], vm.patch_rows_ok):
+        the embedding GEMM writes the padded sequence itself -- no patch gather, no cat, no pad copy; the same tokens."""
+        n_valid = grid[0] * grid[1] + 1
+        t = vm.patch_rows_tokens(self.patch_embed.proj, self.cls_token, rows, n_valid)
+        _, taps = vm.run_blocks(self.blocks, t, n_valid, grid, set(hooks), padded_taps=padded)
+        return [taps[i] for i in hooks], grid, n_valid
+
 
 class ProjectReadout(nn.Module):       # utils.py:28-39
     """cat(tokens[:, 1:], cls expanded) -> Linear(2C -> C) -> GELU, without the concatenation: the linear map splits into
@@ -297,10 +305,14 @@ class BeitBackbone(nn.Module):
         self.act_postprocess3 = _postprocess(vit_features, f[2], [])
         self.act_postprocess4 = _postprocess(vit_features, f[3], [nn.Conv2d(f[3], f[3], 3, 2, 1)])
 
-    def forward(self, x):
+    def forward(self, x, rows=None):
         """forward_beit = forward_adapted_unflatten (utils.py:83-124): readout-project, tokens -> [B, C, h/16, w/16]
-        (run-time grid, not the constructor's), then the per-tap convolutions."""
-        taps, grid, n_valid = self.model.forward_taps(x, self.hooks, padded=True)
+        (run-time grid, not the constructor's), then the per-tap convolutions.  rows: (patch rows, grid) in place of x
+        (Beit.forward_taps_rows)."""
+        if rows is not None:
+            taps, grid, n_valid = self.model.forward_taps_rows(rows[0], rows[1], self.hooks, padded=True)
+        else:
+            taps, grid, n_valid = self.model.forward_taps(x, self.hooks, padded=True)
         outs = []
         for tap, post in zip(taps, (self.act_postprocess1, self.act_postprocess2, self.act_postprocess3, self.act_postprocess4)):
             y = post[0].forward_padded(tap, n_valid)           # ProjectReadout: [B, N-1, C]

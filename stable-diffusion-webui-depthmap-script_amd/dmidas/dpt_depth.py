@@ -78,17 +78,17 @@ class DPT(nn.Module):
         scratch.output_conv = head
         self.scratch = scratch
 
-    def forward(self, x, features=None):               # dpt_depth.py:110-139
+    def forward(self, x, features=None, rows=None):    # dpt_depth.py:110-139
         """features: None, or a dict that receives what ZoeDepth's MidasCore taps with forward hooks
         (dzoedepth/models/base_models/midas.py:307-331): 'l4_rn', 'r4'..'r1' and 'out_conv' (the 32-channel activation
-        after the head's second convolution + ReLU)."""
+        after the head's second convolution + ReLU).  rows: (patch rows, grid) of the image in place of x (infer_batch, BEiT)."""
         if getattr(self, "size_routed", False):
             with vm.size_routed():
-                return self._forward(x, features)
-        return self._forward(x, features)
+                return self._forward(x, features, rows)
+        return self._forward(x, features, rows)
 
-    def _forward(self, x, features=None):
-        l1, l2, l3, l4 = self.pretrained(x)
+    def _forward(self, x, features=None, rows=None):
+        l1, l2, l3, l4 = self.pretrained(x) if rows is None else self.pretrained(x, rows=rows)
         s = self.scratch
         l1, l2, l3, l4 = vm.conv2d(s.layer1_rn, l1), vm.conv2d(s.layer2_rn, l2), vm.conv2d(s.layer3_rn, l3), vm.conv2d(s.layer4_rn, l4)
         path_4 = s.refinenet4(l4, size=l3.shape[2:])
@@ -148,6 +148,24 @@ def midas_net_size(width, height, net_w, net_h, resize_method="minimal", multipl
     return _constrain(scale_w * width, multiple), _constrain(scale_h * height, multiple)
 
 
+def _patch_rows(model, images_u8, net_size, net_h, resize_mode, mean, std, dtype):
+    """(rows, grid) for forward(None, rows=...) where the image can go straight to the padded patch rows of a BEiT backbone's
+    embedding GEMM (ds_preprocess_bicubic_rows: preprocess, patch gather, cls slot and pad rows in one pass), else None."""
+    from .backbones.beit import BeitBackbone
+    pre = getattr(model, "pretrained", None)
+    if not (images_u8.is_cuda and isinstance(pre, BeitBackbone)):
+        return None
+    b, h, w, _ = images_u8.shape
+    nw, nh = midas_net_size(w, h, int(net_size), int(net_size if net_h is None else net_h), resize_mode)
+    conv = pre.model.patch_embed.proj
+    if not (vm.patch_rows_ok(conv, dtype, (nh, nw)) and pre.model.cls_token.dtype == dtype):
+        return None
+    from src import _native
+    grid, _, n_pad, kpad = vm.patch_rows_geometry(conv, (nh, nw), b)
+    rows = _native.preprocess_bicubic_rows(images_u8, (nh, nw), mean, std, conv.kernel_size[0], n_pad, kpad, flip=True, dtype=dtype)
+    return rows, grid
+
+
 class DPTDepthModel(DPT):
     def __init__(self, path=None, non_negative=True, **kwargs):
         features = kwargs.get("features", 256)
@@ -172,8 +190,8 @@ class DPTDepthModel(DPT):
         self.load_state_dict(parameters, strict=False)     # timm's non-persistent buffers may or may not be in the file
 
     @vm.deterministic_forward
-    def forward(self, x, features=None):
-        return super().forward(x, features).squeeze(dim=1)
+    def forward(self, x, features=None, rows=None):
+        return super().forward(x, features, rows).squeeze(dim=1)
 
     @staticmethod
     def preprocess(images_u8, net_size=512, net_h=None, resize_mode="minimal", mean=0.5, std=0.5, dtype=None):
@@ -206,9 +224,17 @@ class DPTDepthModel(DPT):
         not available here: unpinned); prediction upsampled with torch bicubic align_corners=False exactly as :484-489."""
         b, h, w, _ = images_u8.shape
         dtype = self.scratch.layer1_rn.weight.dtype
-        x = self.preprocess(images_u8, net_size, net_h, resize_mode, mean, std, dtype=dtype)
-        if x.is_cuda:
-            x = x.contiguous(memory_format=torch.channels_last)      # (already so: the fused kernel writes channels_last)
-        pred = self.forward(x)
+        rows = _patch_rows(self, images_u8, net_size, net_h, resize_mode, mean, std, dtype)
+        if rows is not None:
+            pred = self.forward(None, rows=rows)
+        else:
+            x = self.preprocess(images_u8, net_size, net_h, resize_mode, mean, std, dtype=dtype)
+            if x.is_cuda:
+                x = x.contiguous(memory_format=torch.channels_last)      # (already so: the fused kernel writes channels_last)
+            pred = self.forward(x)
+        if vm.DEPTH_TAIL and vm.half_on_gpu(pred):
+            # bicubic resize, its rounding to the network's dtype and the widening in one pass (ds_upsample_bicubic_to_f32): same bits
+            from src import _native
+            return _native.upsample_bicubic_to_f32(pred, (h, w))
         pred = F.interpolate(pred.unsqueeze(1), size=(h, w), mode="bicubic", align_corners=False).squeeze(1)
         return pred.float()

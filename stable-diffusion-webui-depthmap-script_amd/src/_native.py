@@ -28,6 +28,7 @@ EXPORTS = [
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
     "ds_bilateral_u16",
+    "ds_preprocess_bicubic_rows", "ds_tokens_fixup", "ds_upsample_bicubic_to_f32", "ds_im2col3x3_s2_nhwc",
 ]
 
 
@@ -92,6 +93,11 @@ def lib():
             L.ds_dpt_head_tail_circular.argtypes = L.ds_dpt_head_tail.argtypes
             L.ds_preprocess_bicubic.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_float),
                                                 ctypes.POINTER(ctypes.c_float), ci, vp]
+            L.ds_preprocess_bicubic_rows.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_float),
+                                                     ctypes.POINTER(ctypes.c_float), ci, ci, ci, ci, vp]
+            L.ds_tokens_fixup.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp]
+            L.ds_upsample_bicubic_to_f32.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
+            L.ds_im2col3x3_s2_nhwc.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
             L.ds_reassemble_readout.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]
             L.ds_bias_act_nhwc.argtypes = [vp, vp, vp, vp, vp, vp, i64, ci, ci, ci, vp]
             L.ds_group_norm_nchw.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ctypes.c_float, ci, ci, vp]
@@ -1108,6 +1114,69 @@ def preprocess_bicubic(images_u8, size_hw, mean, std, flip=True, dtype=None):
     _check(lib().ds_preprocess_bicubic(ctx_for(_dev_index(x)), x.data_ptr(), out.data_ptr(), b, h, w, oh, ow, 1 if flip else 0, m, s, code,
                                        _stream(x)))
     return out
+
+
+def preprocess_bicubic_rows(images_u8, size_hw, mean, std, patch, n_pad, kpad, flip=True, dtype=None, out=None):
+    """uint8 [B,H,W,3] CUDA -> [B, n_pad, kpad] float16 / bfloat16: the zero padded patch rows of the normalised network input, the
+    operand of the patch-embedding GEMM, in one pass (include/depthstereo.h: ds_preprocess_bicubic_rows).  out: a contiguous buffer
+    of that shape to write into (every element of it is written)."""
+    torch = require_gpu()
+    assert images_u8.is_cuda and images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[3] == 3
+    code = {torch.float16: 1, torch.bfloat16: 2}[dtype]
+    x = images_u8.contiguous()
+    b, h, w, _ = x.shape
+    oh, ow = int(size_hw[0]), int(size_hw[1])
+    if out is None:
+        out = torch.empty((b, int(n_pad), int(kpad)), dtype=dtype, device=x.device)
+    assert out.is_contiguous() and out.dtype == dtype and tuple(out.shape) == (b, int(n_pad), int(kpad)) and out.device == x.device
+    m = (ctypes.c_float * 3)(*[float(v) for v in (mean if hasattr(mean, "__len__") else (mean,) * 3)])
+    s = (ctypes.c_float * 3)(*[float(v) for v in (std if hasattr(std, "__len__") else (std,) * 3)])
+    CALLS["ds_preprocess_bicubic_rows"] += 1
+    _check(lib().ds_preprocess_bicubic_rows(ctx_for(_dev_index(x)), x.data_ptr(), out.data_ptr(), b, h, w, oh, ow, 1 if flip else 0, m, s,
+                                            int(patch), int(n_pad), int(kpad), code, _stream(x)))
+    return out
+
+
+def tokens_fixup(tokens, cls, n_valid):
+    """tokens [B, n_pad, C] in place: row 0 of every image <- cls [C], rows n_valid.. <- 0 (include/depthstereo.h: ds_tokens_fixup)."""
+    torch = require_gpu()
+    b, n_pad, c = tokens.shape
+    assert tokens.is_cuda and tokens.is_contiguous() and tokens.dtype in (torch.float16, torch.bfloat16) and c % 8 == 0
+    assert cls.is_cuda and cls.dtype == tokens.dtype and cls.is_contiguous() and cls.numel() == c and 1 <= n_valid <= n_pad
+    CALLS["ds_tokens_fixup"] += 1
+    _check(lib().ds_tokens_fixup(ctx_for(_dev_index(tokens)), tokens.data_ptr(), cls.data_ptr(), b, n_pad, int(n_valid), c,
+                                 1 if tokens.dtype == torch.float16 else 2, _stream(tokens)))
+    return tokens
+
+
+def upsample_bicubic_to_f32(pred, size_hw):
+    """[B, h, w] float16 / bfloat16 CUDA -> float32 [B, H, W]: F.interpolate(pred[:, None], size, mode="bicubic",
+    align_corners=False)[:, 0].float(), bit for bit, in one pass (include/depthstereo.h: ds_upsample_bicubic_to_f32)."""
+    torch = require_gpu()
+    assert pred.is_cuda and pred.dim() == 3 and pred.dtype in (torch.float16, torch.bfloat16)
+    x = pred.contiguous()
+    b, h, w = x.shape
+    oh, ow = int(size_hw[0]), int(size_hw[1])
+    out = torch.empty((b, oh, ow), dtype=torch.float32, device=x.device)
+    CALLS["ds_upsample_bicubic_to_f32"] += 1
+    _check(lib().ds_upsample_bicubic_to_f32(ctx_for(_dev_index(x)), x.data_ptr(), out.data_ptr(), b, h, w, oh, ow,
+                                            1 if x.dtype == torch.float16 else 2, _stream(x)))
+    return out
+
+
+def im2col3x3_s2(x, circular=False):
+    """NCHW-shaped float16 / bfloat16 CUDA tensor in channels_last memory -> [B * ho * wo, 9 * C]: the 3x3 / stride 2 / padding 1
+    windows in [ky, kx, c] order, zero or circular padding (include/depthstereo.h: ds_im2col3x3_s2_nhwc)."""
+    torch = require_gpu()
+    b, c, h, w = x.shape
+    assert x.is_cuda and x.dtype in (torch.float16, torch.bfloat16) and c % 8 == 0
+    xin = x.contiguous(memory_format=torch.channels_last)
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    rows = torch.empty((b * ho * wo, 9 * c), dtype=x.dtype, device=x.device)
+    CALLS["ds_im2col3x3_s2_nhwc"] += 1
+    _check(lib().ds_im2col3x3_s2_nhwc(ctx_for(_dev_index(x)), xin.data_ptr(), rows.data_ptr(), b, h, w, c, 1 if circular else 0,
+                                      1 if x.dtype == torch.float16 else 2, _stream(x)))
+    return rows
 
 
 def upsample_bilinear(x, size=None, scale_factor=None, align_corners=True):

@@ -507,6 +507,12 @@ def run_blocks(blocks, x, n_valid, grid_hw, take, padded_taps=False):
     return x, taps
 
 
+# A/B switches of the forward's two ends (csrc/ds_forward_ends.hip); "0" gives the route each one replaced, bit-identical results:
+PATCH_ROWS = os.environ.get("DS_PATCH_ROWS", "1") != "0"            # image -> padded patch rows in one pass, cls / pad rows by ds_tokens_fixup
+DEPTH_TAIL = os.environ.get("DS_DEPTH_TAIL", "1") != "0"            # prediction -> float32 [B, H, W]: bicubic + widening in one pass
+IM2COL_HIP = os.environ.get("DS_IM2COL", "1") != "0"                # the strided 3x3's windows by one gather kernel
+
+
 def interpolate_bilinear(x, size=None, scale_factor=None, align_corners=True):
     """F.interpolate(mode="bilinear") of the DPT decoders: the HIP kernel for half-precision channels_last activations on
     the GPU (one pass at HBM speed), torch everywhere else (float32 parity path, CPU)."""
@@ -646,6 +652,36 @@ def patch_embed_tokens(conv, x):
     return y.view(b, gh * gw, conv.out_channels)
 
 
+def patch_rows_ok(conv, dtype, size_hw):
+    """True where image -> tokens can run as ds_preprocess_bicubic_rows -> ds_linear -> ds_tokens_fixup: the conditions of
+    patch_embed_hip_ok for the network input that ds_preprocess_bicubic would have written (half precision, channels_last, size_hw),
+    with both switches on.  The tokens are bit for bit those of preprocess -> patch_embed_tokens -> cat(cls) -> pad_tokens."""
+    if not (PATCH_ROWS and PREPROCESS_HIP and not STOCK[0] and invariant() and LINEAR_HIP == "all" and type(conv) is nn.Conv2d
+            and dtype in (torch.float16, torch.bfloat16) and conv.weight.dtype == dtype):
+        return False
+    k = conv.kernel_size
+    return (k[0] == k[1] and k[0] <= 32 and tuple(conv.stride) == tuple(k) and tuple(conv.padding) == (0, 0) and conv.groups == 1
+            and tuple(conv.dilation) == (1, 1) and conv.out_channels % 256 == 0 and conv.in_channels == 3
+            and size_hw[0] >= k[0] and size_hw[1] >= k[1])
+
+
+def patch_rows_geometry(conv, size_hw, batch):
+    """(grid, n_valid, n_pad, kpad) of the token buffer for a network input of size_hw: cls + patches, padded by pad_len."""
+    p = conv.kernel_size[0]
+    grid = (size_hw[0] // p, size_hw[1] // p)
+    n_valid = grid[0] * grid[1] + 1
+    return grid, n_valid, pad_len(n_valid, batch), (3 * p * p + 127) // 128 * 128
+
+
+def patch_rows_tokens(conv, cls_token, rows, n_valid):
+    """rows [B, n_pad, kpad] (ds_preprocess_bicubic_rows) -> the padded token sequence [B, n_pad, C]: ONE GEMM over every row of the
+    buffer (the cls and pad rows are zero rows of the operand), then ds_tokens_fixup writes the cls token and the zero pad rows."""
+    from . import _native
+    b, n_pad, kpad = rows.shape
+    t = _native.linear(rows.view(b * n_pad, kpad), _gemm_weight(conv, rows, kpad), conv.bias).view(b, n_pad, conv.out_channels)
+    return _native.tokens_fixup(t, cls_token.detach().reshape(-1), n_valid)
+
+
 def strided3x3_hip_ok(layer, x):
     """The strided 3x3 of the reassemble stage (act_postprocess4 / resize_layers[3]: Conv2d(C, C, 3, stride 2, padding 1))."""
     if not (invariant() and LINEAR_HIP == "all" and half_on_gpu(x) and x.dim() == 4 and type(layer) is nn.Conv2d):
@@ -656,17 +692,28 @@ def strided3x3_hip_ok(layer, x):
             and layer.in_channels % 128 == 0 and 9 * layer.in_channels <= 16384 and x.shape[1] == layer.in_channels)
 
 
+def strided3x3_rows(x, circular, hip=None):
+    """[B * ho * wo, 9 * C]: the 3x3 / stride 2 windows of the zero (circular) padded map in [ky, kx, c] order.  One gather kernel
+    (ds_im2col3x3_s2_nhwc); DS_IM2COL=0 / hip=False: pad, NHWC copy and a strided view copied to rows -- three passes, the same rows."""
+    b, c, h, w = x.shape
+    if (IM2COL_HIP if hip is None else hip) and c % 8 == 0:
+        from . import _native
+        return _native.im2col3x3_s2(x, circular)
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    xp = F.pad(x, (1, 1, 1, 1), mode="circular") if circular else F.pad(x, (1, 1, 1, 1))
+    xp = xp.permute(0, 2, 3, 1).contiguous()                              # [B, h + 2, w + 2, C]
+    sb, sh, sw, sc = xp.stride()
+    return xp.as_strided((b, ho, wo, 3, 3, c), (sb, 2 * sh, 2 * sw, sh, sw, sc)).reshape(b * ho * wo, 9 * c)
+
+
 def conv_strided3x3(layer, x):
     """layer(x) for a 3x3 / stride 2 / padding 1 convolution as gather + GEMM: the 3 x 3 windows of the zero padded (TILING_MODE:
-    circularly padded) NHWC map are gathered once ([B, ho, wo, 3, 3, C], a strided view copied to rows), then ds_linear with the
-    bias in its epilogue."""
+    circularly padded) NHWC map are gathered once (strided3x3_rows: [B * ho * wo, 9 * C]), then ds_linear with the bias in its
+    epilogue."""
     from . import _native
     b, c, h, w = x.shape
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-    xp = F.pad(x, (1, 1, 1, 1), mode="circular") if layer.padding_mode == "circular" else F.pad(x, (1, 1, 1, 1))
-    xp = xp.permute(0, 2, 3, 1).contiguous()                              # [B, h + 2, w + 2, C]
-    sb, sh, sw, sc = xp.stride()
-    rows = xp.as_strided((b, ho, wo, 3, 3, c), (sb, 2 * sh, 2 * sw, sh, sw, sc)).reshape(b * ho * wo, 9 * c)
+    rows = strided3x3_rows(x, layer.padding_mode == "circular")
     y = _native.linear(rows, _gemm_weight(layer, x, 9 * c), layer.bias)
     return y.view(b, ho, wo, layer.out_channels).permute(0, 3, 1, 2)
 PREPROCESS_HIP = os.environ.get("DS_PREPROCESS", "1") != "0"      # A/B switch: ds_preprocess_bicubic vs the torch chain
