@@ -239,6 +239,38 @@ int ds_bilateral_u16(ds_ctx *ctx, const uint16_t *depth, int n, int h, int w, in
                      int wrap, double *out, void *stream);
 
 /*
+ * ds_frame_luma_hist -- per-frame luma histograms of a uint8 clip: the input of video mode's scene-cut detector (the reference
+ * leaves cut detection as a TODO, src/video_mode.py:114, and has no implementation; this comment is the definition).
+ * frames [n,h,w,c] uint8, dense, ANY byte alignment -> hist [n,256] uint32: hist[f][v] = the number of pixels of frame f with Y == v.
+ *   c == 1: Y = the sample.  c == 3 or 4: Y = (77 R + 150 G + 29 B + 128) >> 8 in integer arithmetic on channels 0, 1, 2 (the
+ *   weights sum to 256: Y lies in 0..255, white gives 255); channel 3 is ignored.
+ * The entry point OVERWRITES hist (it does not accumulate; the caller need not clear it).  Counts are integers: every summation
+ * order gives the same bits, a frame's row does not depend on the batch, and np.bincount on the same Y is the model
+ * (tests/video_cuts_cases.py).
+ * DS_EINVAL: a null pointer; n, h or w <= 0; c outside {1, 3, 4}; hist not 4-byte aligned.  DS_EUNSUPPORTED: h * w >= 2^32, or
+ * n > 65535.  Asynchronous on `stream` (a clear of hist and one kernel); no allocation, no workspace.
+ */
+int ds_frame_luma_hist(ds_ctx *ctx, const uint8_t *frames, int n, int h, int w, int c, uint32_t *hist, void *stream);
+
+/*
+ * ds_temporal_smooth5_f32 -- the 5-tap temporal filter of video mode's 'experimental' smoothening (src/video_mode.py:119-124) on a
+ * run of frames whose taps are clamped to [lo, hi]: with lo and hi the first and last frame of a scene nothing is smoothed across
+ * a cut; with lo = 0 and hi = m - 1 it is the reference's clip().
+ * src [m, plane] float32 -> out [count, plane] float32; out must not overlap src.  For j < count, i = first + j,
+ * W = float32 {0.10, 0.20, 0.40, 0.20, 0.10} and k_u = min(max(i + u - 2, lo), hi):
+ *   out[j][p] = ((((+0.0f + W0 * src[k_0][p]) + W1 * src[k_1][p]) + W2 * src[k_2][p]) + W3 * src[k_3][p]) + W4 * src[k_4][p]
+ * every product rounded to binary32, then every sum rounded to binary32: no fused multiply-add, subnormals kept.  That is the
+ * reference's `f += mul * predictions[clip(...)]` on float32 frames, operation for operation: a NumPy loop with these roundings
+ * gives the same bits (tests/video_cuts_cases.py).  Which NaN comes out of inf - inf is not specified.
+ * A caller whose frames are sharded passes src = its halo plus its frames and first / lo / hi as indices into that.
+ * DS_EINVAL: a null pointer; m, plane or count <= 0; 0 <= lo <= first, first + count - 1 <= hi or hi < m broken; src or out not
+ * 4-byte aligned (any other alignment and any plane are legal); out overlapping src.  DS_EUNSUPPORTED: plane > 2^32.
+ * Asynchronous on `stream`; one kernel, no workspace.
+ */
+int ds_temporal_smooth5_f32(ds_ctx *ctx, const float *src, int m, int64_t plane, int first, int count, int lo, int hi, float *out,
+                            void *stream);
+
+/*
  * ds_normalmap_selfcheck -- device self-test of the fused normal-map kernels' arithmetic (tests): their square root and reciprocal
  * are the generic float64 expansions WITHOUT range scaling and special-case fix-ups (dead for n^2 = zx^2 + zy^2 + 1 in [1, 2^22],
  * src/normalmap_generation.py:34-39); the kernel compares them with sqrt() and 1.0 / n on n^2 = K / 2^18, K = k0 + stride * i,

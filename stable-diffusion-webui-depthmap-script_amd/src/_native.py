@@ -27,7 +27,7 @@ EXPORTS = [
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
-    "ds_bilateral_u16",
+    "ds_bilateral_u16", "ds_frame_luma_hist", "ds_temporal_smooth5_f32",
     "ds_preprocess_bicubic_rows", "ds_tokens_fixup", "ds_upsample_bicubic_to_f32", "ds_im2col3x3_s2_nhwc",
 ]
 
@@ -79,6 +79,8 @@ def lib():
             for name in ("ds_normalmap", "ds_normalmap_f64", "ds_normalmap_gradient_f32", "ds_normalmap_gradient_f16", "ds_normalmap_gradient_blur_f32"):
                 getattr(L, name + "_wrap").argtypes = getattr(L, name).argtypes
             L.ds_bilateral_u16.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, ci, vp, vp]
+            L.ds_frame_luma_hist.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
+            L.ds_temporal_smooth5_f32.argtypes = [vp, vp, ci, i64, ci, ci, ci, ci, vp, vp]
             L.ds_depth_to_u16.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp]
             L.ds_convert_to_i16.argtypes = [vp, vp, ci, i64, vp, vp]
             L.ds_stereo_last_stats.argtypes = [vp, ctypes.POINTER(i64), vp]
@@ -365,6 +367,50 @@ def bilateral_u16(depth_u16, d, sigma_color, sigma_space, wrap=False):
     CALLS["ds_bilateral_u16"] += 1
     _check(lib().ds_bilateral_u16(ctx_for(_dev_index(depth_u16)), depth_u16.data_ptr(), n, h, w, d // 2, tabs[0].data_ptr(),
                                   tabs[1].data_ptr(), 1 if wrap else 0, out.data_ptr(), _stream(depth_u16)))
+    return out
+
+
+# ---- video mode (csrc/ds_video.hip; host half: src/video_mode.py) ------------------------------------------------------------------
+def frame_luma_hist(frames_u8, out=None):
+    """Per-frame histograms of the integer luma (ds_frame_luma_hist, include/depthstereo.h) of a dense uint8 cuda clip [n,h,w] or
+    [n,h,w,c], c in {1, 3, 4}, at any byte alignment.  Returns [n,256] int32 whose BITS are the uint32 counts (torch has no
+    arithmetic on uint32; a count of 2^31 or more reads negative until masked).  out: write into this [n,256] int32 cuda tensor; it is
+    overwritten, not added to."""
+    torch = require_gpu()
+    if not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() in (3, 4)
+            and frames_u8.is_contiguous()):
+        raise DepthStereoError("frame_luma_hist: frames must be a contiguous uint8 cuda tensor [n,h,w] or [n,h,w,c], got %s %s"
+                               % (getattr(frames_u8, "dtype", type(frames_u8)), tuple(getattr(frames_u8, "shape", ()))))
+    n, h, w = frames_u8.shape[:3]
+    c = frames_u8.shape[3] if frames_u8.dim() == 4 else 1
+    if out is None:
+        out = torch.empty((n, 256), dtype=torch.int32, device=frames_u8.device)
+    elif not (out.is_cuda and out.device == frames_u8.device and out.dtype == torch.int32 and tuple(out.shape) == (n, 256)
+              and out.is_contiguous()):
+        raise DepthStereoError("frame_luma_hist: out must be a contiguous int32 [%d,256] tensor on the frames' device" % n)
+    CALLS["ds_frame_luma_hist"] += 1
+    _check(lib().ds_frame_luma_hist(ctx_for(_dev_index(frames_u8)), frames_u8.data_ptr(), n, h, w, c, out.data_ptr(), _stream(frames_u8)))
+    return out
+
+
+def temporal_smooth5(src, first, count, lo, hi, out=None):
+    """The clamped 5-tap temporal filter (ds_temporal_smooth5_f32, include/depthstereo.h): src float32 cuda [m, ...] contiguous ->
+    float32 [count, ...], frames first .. first + count - 1 of src smoothed with taps clamped to frames lo..hi.  out: write into this
+    contiguous float32 tensor of that shape (it must not overlap src)."""
+    torch = require_gpu()
+    if not (torch.is_tensor(src) and src.is_cuda and src.dtype == torch.float32 and src.dim() >= 1 and src.is_contiguous()):
+        raise DepthStereoError("temporal_smooth5: src must be a contiguous float32 cuda tensor [m, ...], got %s %s"
+                               % (getattr(src, "dtype", type(src)), tuple(getattr(src, "shape", ()))))
+    m = src.shape[0]
+    plane = src[0].numel() if m else 0
+    shape = (max(int(count), 0),) + tuple(src.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    elif not (out.is_cuda and out.device == src.device and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()):
+        raise DepthStereoError("temporal_smooth5: out must be a contiguous float32 %s tensor on src's device" % (shape,))
+    CALLS["ds_temporal_smooth5_f32"] += 1
+    _check(lib().ds_temporal_smooth5_f32(ctx_for(_dev_index(src)), src.data_ptr(), m, plane, int(first), int(count), int(lo), int(hi),
+                                         out.data_ptr(), _stream(src)))
     return out
 
 

@@ -13,26 +13,35 @@ What is built: the COMPUTE of video mode on frame tensors --
     interpolation between the two neighbouring order statistics reproduced) -- no rank ever holds all frames;
   * ``gen_frames_sharded``: two passes over this rank's contiguous block of frames (network batched on the device,
     normalisation with the collectives above, depth -> uint16 -> stereo on the device) and a single gather of the
-    collated output to rank 0 (src/multigpu.gather_units; RCCL over xGMI under the 'nccl' backend).
+    collated output to rank 0 (src/multigpu.gather_units; RCCL over xGMI under the 'nccl' backend);
+  * scene cuts, the reference's TODO at :114 ("Detect cuts and process segments separately"): ``cut_scores`` / ``detect_cuts``
+    compare the luma histograms of neighbouring frames (csrc/ds_video.hip on the device, torch.bincount on the host, sharded: one
+    all-gather of 1 KB per frame), and ``cuts=`` on the three functions above normalises every scene as the reference normalises a
+    clip.  The 5-tap filter of float32 device frames is a kernel of the same file (DS_VIDEO_SMOOTH=0: torch passes).
 Container I/O (moviepy / imageio-ffmpeg / av: open_path_as_images :13-64, frames_to_video :67-100) is outside the hot
 path and not built; callers hand in decoded frames.
 """
 import numpy as np
 
 
-def process_predicitons(predictions, smoothening='none'):
+def process_predicitons(predictions, smoothening='none', cuts=None):
     """Drop-in for the reference's process_predicitons (:103-128; the spelling is the reference's): a list of [H,W]
     arrays in, a list of normalised arrays out ('none': float32, global min/max; 'experimental': float64, the 0.5 / 99.5
     percentiles of the 5-tap temporally smoothed clip; anything else: returned unchanged).  The work is the same tensor
     code that runs frame-parallel (process_predictions_sharded) on the whole clip as one local shard -- on the GPU when
-    one is visible; nothing here is specific to a device."""
+    one is visible; nothing here is specific to a device.
+    cuts (not in the reference, which leaves it as a TODO at :114): frame indices at which a new scene starts, strictly
+    increasing, in 1..F-1 (ValueError otherwise; detect_cuts makes such a list).  The result is then the reference's function
+    applied to every scene on its own, concatenated.  None or []: the whole clip is one scene."""
+    if cuts:
+        _check_cuts(cuts, len(predictions))
     if smoothening not in ('none', 'experimental') or len(predictions) == 0:
         return predictions
     import torch
     stack = torch.from_numpy(np.stack([np.asarray(p, dtype=np.float32) for p in predictions]))
     if torch.cuda.is_available():
         stack = stack.cuda()
-    out = process_predictions_sharded(stack, smoothening, group=_LOCAL).cpu().numpy()
+    out = process_predictions_sharded(stack, smoothening, group=_LOCAL, cuts=cuts).cpu().numpy()
     return [out[i] for i in range(out.shape[0])]
 
 
@@ -108,33 +117,105 @@ def _global_percentiles(local, qs, group):
     return out
 
 
-def process_predictions_sharded(local, smoothening='none', group=None):
+def _scale_f64(x, a, b):
+    """global_scaling(objs, a, b) of the reference (:104-111) with float64 percentiles: (x - a) / (b - a) in float64.  The divisor
+    is handed to torch as a TENSOR: on the device a division by a host scalar is computed as a product with its reciprocal, which
+    is off by one unit in the last place in a share of the pixels; tensor by tensor is a true IEEE division on either device."""
+    import torch
+    return (x.double() - a) / torch.tensor(b - a, dtype=torch.float64, device=x.device)
+
+
+def _check_cuts(cuts, n_frames):
+    """cuts: global frame indices, strictly increasing, each in 1..n_frames-1 (the first frame of a new scene)."""
+    prev = 0
+    for c in cuts:
+        if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)):
+            raise ValueError("cuts must be integers, got %r" % (c,))
+        if not prev < c <= n_frames - 1:
+            raise ValueError("cuts must be strictly increasing frame indices in 1..%d, got %r" % (n_frames - 1, list(cuts)))
+        prev = int(c)
+
+
+def _shard_counts(n_local, device, group):
+    """Frames per rank of the group (one all-gather; [n_local] without a group)."""
+    import torch
+    import torch.distributed as dist
+    if not _is_multi(group):
+        return [n_local]
+    counts = [torch.zeros(1, dtype=torch.int64, device=device) for _ in range(dist.get_world_size(group))]
+    dist.all_gather(counts, torch.tensor([n_local], dtype=torch.int64, device=device), group=group)
+    return [int(c.item()) for c in counts]
+
+
+def _segments(cuts, start, n_local, n_frames):
+    """The scenes of a clip of n_frames frames cut at `cuts`, seen from the rank that holds frames start .. start + n_local - 1:
+    a list of (g0, g1, ls, le) -- the scene is global frames [g0, g1), of which this rank holds local[ls:le] (ls == le: none)."""
+    bounds = [0] + [int(c) for c in cuts] + [n_frames]
+    out = []
+    for g0, g1 in zip(bounds[:-1], bounds[1:]):
+        ls = min(max(g0 - start, 0), n_local)
+        le = min(max(g1 - start, ls), n_local)
+        out.append((g0, g1, ls, le))
+    return out
+
+
+def _kernel_smooth():
+    """DS_VIDEO_SMOOTH=0 sends float32 device frames through the torch passes too (the route CPU tensors always take)."""
+    import os
+    return os.environ.get('DS_VIDEO_SMOOTH', '1') != '0'
+
+
+def process_predictions_sharded(local, smoothening='none', group=None, cuts=None):
     """The normalisation of process_predicitons for frames sharded in CONTIGUOUS blocks over the ranks.
     local: float32 tensor [n_local, H, W] (this rank's frames, any device).  Returns the normalised tensor (float64 for
-    'experimental', like numpy's promotion with the float64 percentiles; float32 for 'none')."""
+    'experimental', like numpy's promotion with the float64 percentiles; float32 for 'none').
+    cuts: GLOBAL frame indices at which a new scene starts (the same list on every rank; ValueError unless strictly increasing
+    in 1..F-1); every scene is normalised on its own -- 'none': the per-scene pairs (min, -max) in ONE all-reduce(MIN) of an
+    [S, 2] tensor; 'experimental': the taps of the temporal filter are clamped to the scene (its bounds in global indices,
+    intersected with this rank's frames and halo), its percentiles are the scene's -- a scene may span several ranks, and ranks
+    that hold no frame of it take part in its collectives with empty data.  None or []: the clip is one scene.
+    The 5-tap filter of float32 device frames is ONE kernel launch per scene (_native.temporal_smooth5, csrc/ds_video.hip;
+    DS_VIDEO_SMOOTH=0: the five torch passes that CPU tensors take); same bits either way."""
     import torch
     import torch.distributed as dist
     multi = _is_multi(group)               # the _LOCAL sentinel is handed on as it is: the percentile helpers honour it too
-    if smoothening == 'none':
+    cuts = list(cuts) if cuts is not None else []
+    if smoothening not in ('none', 'experimental'):
+        return local
+    n_local = local.shape[0]
+    counts = _shard_counts(n_local, local.device, group) if (cuts or smoothening == 'experimental') else None
+    rank = dist.get_rank(group) if multi else 0
+    world = dist.get_world_size(group) if multi else 1
+    segs = None
+    if cuts:
+        _check_cuts(cuts, sum(counts))
+        segs = _segments(cuts, sum(counts[:rank]), n_local, sum(counts))
+    if smoothening == 'none' and not cuts:
         mm = torch.stack((local.min(), -local.max())) if local.numel() else torch.tensor([float('inf')] * 2, device=local.device)
         if multi:
             dist.all_reduce(mm, op=dist.ReduceOp.MIN, group=group)          # min and (negated) max in one collective
         mn, mx = mm[0], -mm[1]
         return (local - mn) / (mx - mn)
-    if smoothening != 'experimental':
-        return local
-    rank = dist.get_rank(group) if multi else 0
-    world = dist.get_world_size(group) if multi else 1
-    n_local = local.shape[0]
+    if smoothening == 'none':
+        mm = torch.full((len(segs), 2), float('inf'), dtype=local.dtype, device=local.device)
+        for i, (_, _, ls, le) in enumerate(segs):
+            if le > ls:
+                mm[i, 0] = local[ls:le].min()
+                mm[i, 1] = -local[ls:le].max()
+        if multi:
+            dist.all_reduce(mm, op=dist.ReduceOp.MIN, group=group)          # every scene's min and (negated) max in one collective
+        out = torch.empty_like(local)
+        for i, (_, _, ls, le) in enumerate(segs):
+            if le > ls:
+                mn, mx = mm[i, 0], -mm[i, 1]
+                out[ls:le] = (local[ls:le] - mn) / (mx - mn)
+        return out
     # halo: the two frames before and after this rank's block (the global first / last frame replicated: clip() of the
     # reference).  Every rank publishes its first and last (up to) two frames -- zero placeholders where it holds fewer,
     # so the collectives have one fixed shape even for empty shards -- and walks outwards over its neighbours until it
     # has two frames on each side (a neighbour may hold a single frame, or none).
     hw = tuple(local.shape[1:])
     if multi:
-        counts = [torch.zeros(1, dtype=torch.int64, device=local.device) for _ in range(world)]
-        dist.all_gather(counts, torch.tensor([n_local], dtype=torch.int64, device=local.device), group=group)
-        counts = [int(c.item()) for c in counts]
         k = min(n_local, 2)
         head = torch.zeros((2,) + hw, dtype=local.dtype, device=local.device)
         tail = torch.zeros((2,) + hw, dtype=local.dtype, device=local.device)
@@ -166,16 +247,143 @@ def process_predictions_sharded(local, smoothening='none', group=None):
         last = after[-1] if after else local[-1]
         left = torch.stack([first] * (2 - len(before)) + before)
         right = torch.stack(after + [last] * (2 - len(after)))
-    ext = torch.cat((left, local, right), dim=0)
-    processed = torch.zeros_like(local)
-    for u, mul in enumerate([0.10, 0.20, 0.40, 0.20, 0.10]):                # same order of accumulation as the reference
-        processed += mul * ext[u:u + n_local]
-    a, b = _global_percentiles(processed, [0.5, 99.5], group)
-    return (local.double() - a) / (b - a)
+    kernel = local.is_cuda and local.dtype == torch.float32 and _kernel_smooth()
+    if not cuts and not kernel:
+        ext = torch.cat((left, local, right), dim=0)
+        processed = torch.zeros_like(local)
+        for u, mul in enumerate([0.10, 0.20, 0.40, 0.20, 0.10]):            # same order of accumulation as the reference
+            processed += mul * ext[u:u + n_local]
+        a, b = _global_percentiles(processed, [0.5, 99.5], group)
+        return _scale_f64(local, a, b)
+    # Per scene, or on the kernel route.  Every tap index is clamped to the scene, so one rank alone needs no halo at all (the
+    # clamp is the reference's clip()); sharded, ext[0] is global frame start - 2, and a scene that starts at the clip's first
+    # frame never reaches the replicated placeholders in front of it (likewise at the end).
+    start, total = sum(counts[:rank]), sum(counts)
+    if segs is None:
+        segs = [(0, total, 0, n_local)]
+    local = local.contiguous()
+    ext, off = (torch.cat((left, local, right), dim=0), 2) if multi else (local, 0)
+    m = ext.shape[0]
+    processed = torch.empty_like(local)
+    for g0, g1, ls, le in segs:
+        if le == ls:
+            continue
+        lo, hi = max(g0 - start + off, 0), min(g1 - 1 - start + off, m - 1)
+        if kernel:
+            from . import _native
+            _native.temporal_smooth5(ext, ls + off, le - ls, lo, hi, out=processed[ls:le])
+            continue
+        idx = torch.arange(ls + off, le + off, device=local.device)
+        acc = torch.zeros_like(local[ls:le])
+        for u, mul in enumerate([0.10, 0.20, 0.40, 0.20, 0.10]):            # same order of accumulation as the reference
+            acc += mul * ext.index_select(0, (idx + (u - 2)).clamp(lo, hi))
+        processed[ls:le] = acc
+    out = torch.empty(local.shape, dtype=torch.float64, device=local.device)
+    for g0, g1, ls, le in segs:                                             # every rank, also one without a frame of the scene
+        a, b = _global_percentiles(processed[ls:le], [0.5, 99.5], group)
+        if le > ls:
+            out[ls:le] = _scale_f64(local[ls:le], a, b)
+    return out
 
 
-def gen_frames_sharded(frames_u8, predict_batch, inp, smoothening='none', group=None, batch=8, dst=0, invert=False):
+# ---- scene cuts -----------------------------------------------------------------------------------------------------------------
+# The reference has no cut detector (:114 is a TODO); the rule below and the comment of ds_frame_luma_hist in include/depthstereo.h
+# are the definition.  Everything is integer arithmetic up to one float64 division per frame, so the device route, the host route
+# and a sharded run agree bit for bit and every rank derives the same cut list.
+def _as_frames(frames_u8):
+    import torch
+    f = torch.from_numpy(np.ascontiguousarray(frames_u8)) if isinstance(frames_u8, np.ndarray) else frames_u8
+    if not (torch.is_tensor(f) and f.dtype == torch.uint8 and f.dim() in (3, 4) and (f.dim() == 3 or f.shape[3] in (1, 3, 4))):
+        raise ValueError("frames must be uint8 [F,H,W] or [F,H,W,C] with C in {1, 3, 4}, got %s %s"
+                         % (getattr(f, "dtype", type(f)), tuple(getattr(f, "shape", ()))))
+    return f
+
+
+def _luma_hist(frames):
+    """int64 [n, 256] on the frames' device: the pixels of every frame per integer luma Y (grey: the sample; RGB / RGBA:
+    (77 R + 150 G + 29 B + 128) >> 8).  Device frames: the kernel; host frames: torch.bincount on the same Y."""
+    import torch
+    n = frames.shape[0]
+    if n == 0:
+        return torch.zeros((0, 256), dtype=torch.int64, device=frames.device)
+    if frames.is_cuda:
+        from . import _native
+        return _native.frame_luma_hist(frames.contiguous()).to(torch.int64) & 0xffffffff
+    rows = []
+    for f in frames:                                                        # frame by frame: int64 copies of one frame, not of the clip
+        if f.dim() == 2 or f.shape[2] == 1:
+            y = f.reshape(-1).to(torch.int64)
+        else:
+            c = f.reshape(-1, f.shape[2]).to(torch.int64)
+            y = (77 * c[:, 0] + 150 * c[:, 1] + 29 * c[:, 2] + 128) >> 8
+        rows.append(torch.bincount(y, minlength=256))
+    return torch.stack(rows)
+
+
+def _cut_scores_local(local_frames, n_frames, bins, group):
+    """cut_scores from this rank's contiguous block of frames (multigpu.shard_bounds): the [n_local, 256] tables are all-gathered
+    as uint32 bits, 1 KB per frame, padded to the largest shard (empty shards take part), and every rank computes all scores."""
+    import torch
+    import torch.distributed as dist
+    from . import multigpu
+    if bins not in (2, 4, 8, 16, 32, 64, 128, 256):
+        raise ValueError("bins must be a power of two in 2..256, got %r" % (bins,))
+    table = _luma_hist(local_frames)
+    if _is_multi(group):
+        bounds = multigpu.shard_bounds(n_frames, dist.get_world_size(group))
+        assert bounds[dist.get_rank(group)][1] - bounds[dist.get_rank(group)][0] == local_frames.shape[0]
+        per = max(e - s for s, e in bounds)
+        pad = torch.zeros((per, 256), dtype=torch.int32, device=table.device)
+        pad[:table.shape[0]] = table.to(torch.int32)                        # the low 32 bits: a count of 2^31 or more wraps, and is masked back
+        parts = [torch.empty_like(pad) for _ in bounds]
+        dist.all_gather(parts, pad, group=group)
+        table = torch.cat([p[:e - s] for p, (s, e) in zip(parts, bounds)]).to(torch.int64) & 0xffffffff
+    hist = table.cpu().numpy()
+    assert hist.shape == (n_frames, 256)
+    npix = int(np.prod(local_frames.shape[1:3]))
+    folded = hist.reshape(n_frames, bins, 256 // bins).sum(axis=2)          # neighbours summed: exact
+    score = np.zeros(n_frames, dtype=np.float64)
+    if n_frames > 1:
+        score[1:] = np.abs(np.diff(folded, axis=0)).sum(axis=1).astype(np.float64) / np.float64(2 * npix)
+    return score
+
+
+def cut_scores(frames_u8, bins=64, group=None):
+    """How much the luma histogram changes from frame t - 1 to frame t: float64 [F] in [0, 1], score[0] = 0.
+    frames_u8: the whole clip, uint8 [F,H,W] or [F,H,W,C] (C = 1, 3 or 4; torch tensor on any device, or numpy).  The 256-bin
+    histograms are folded to `bins` (a power of two in 2..256) by summing neighbours, S_t = sum_b |H_t[b] - H_{t-1}[b]| in int64,
+    score[t] = S_t / (2 H W) as one float64 division.  With a process group each rank histograms its own block of frames
+    (multigpu.my_shard) and the tables are all-gathered; every rank returns the same vector."""
+    import torch.distributed as dist
+    from . import multigpu
+    frames = _as_frames(frames_u8)
+    s, e = 0, frames.shape[0]
+    if _is_multi(group):
+        s, e = multigpu.my_shard(frames.shape[0], dist.get_rank(group), dist.get_world_size(group))
+    return _cut_scores_local(frames[s:e], frames.shape[0], bins, group)
+
+
+def _cuts_from_scores(score, threshold, min_len):
+    cuts, prev, n = [], 0, len(score)
+    for t in range(1, n):
+        if score[t] > threshold and t - prev >= min_len and n - t >= min_len:
+            cuts.append(t)
+            prev = t
+    return cuts
+
+
+def detect_cuts(frames_u8, threshold=0.4, min_len=1, bins=64, group=None):
+    """Scene cuts of a clip: the sorted list of the frames t in 1..F-1 (each the FIRST frame of a new scene), scanned upwards,
+    with cut_scores(...)[t] > threshold that lie at least min_len frames after the previous cut (or the start) and at least
+    min_len frames before the end of the clip.  The default threshold is a starting point, not a measured optimum."""
+    return _cuts_from_scores(cut_scores(frames_u8, bins, group), threshold, min_len)
+
+
+def gen_frames_sharded(frames_u8, predict_batch, inp, smoothening='none', group=None, batch=8, dst=0, invert=False,
+                       cuts=None, cut_threshold=0.4, cut_min_len=1):
     """Two-pass video pipeline on decoded frames, frame parallel.
+    cuts: None -- the clip is one scene; 'auto' -- detect_cuts(threshold=cut_threshold, min_len=cut_min_len) on the decoded frames,
+    each rank on its own block; a list -- used as given.  With cuts the result on rank `dst` also has the key 'cuts' (the list).
     frames_u8: uint8 tensor [F, H, W, 3] (every rank may hold the full clip or just index its block); predict_batch:
     callable uint8 [b,H,W,3] -> float32 [b,H,W] raw prediction (e.g. DepthAnythingV2.infer_batch) on the rank's device.
     invert: True for the models whose raw output is near-is-dark (ids 0, 7-9, 10: depthmap_generation.py:402) -- the
@@ -197,7 +405,13 @@ def gen_frames_sharded(frames_u8, predict_batch, inp, smoothening='none', group=
     preds = torch.cat(preds) if preds else torch.empty((0,) + tuple(frames_u8.shape[1:3]), device=dev)
     if invert:
         preds = preds * -1                                                                        # core.py:192-195
-    norm = process_predictions_sharded(preds, smoothening, group)                                 # :151
+    if isinstance(cuts, str):
+        if cuts != 'auto':
+            raise ValueError("cuts must be None, 'auto' or a list of frame indices, got %r" % (cuts,))
+        cuts = _cuts_from_scores(_cut_scores_local(mine, n, 64, group), cut_threshold, cut_min_len)
+    elif cuts is not None:
+        cuts = list(cuts)
+    norm = process_predictions_sharded(preds, smoothening, group, cuts=cuts)                      # :151
     # second pass: the normalised frames re-enter the funnel as custom depth maps, np.asarray(dp, dtype='float') = float64
     # (core.py:170-174), and are quantised in float64 (:211) -- also in 'none' mode, whose frames are float32
     if e > s:
@@ -218,4 +432,6 @@ def gen_frames_sharded(frames_u8, predict_batch, inp, smoothening='none', group=
             gathered[k] = None if g is None else g.view(torch.uint16)
         else:
             gathered[k] = multigpu.gather_units(v, n, group=group, dst=dst)
+    if cuts is not None:
+        gathered['cuts'] = cuts
     return gathered if rank == dst else None
