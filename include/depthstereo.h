@@ -543,6 +543,48 @@ int ds_linear_readout(ds_ctx *ctx, const void *x, const void *w_tok, const void 
                       int64_t tokens_padded, int64_t tokens, int64_t out_features, int64_t in_features, int dtype, void *stream);
 
 /*
+ * ds_conv3x3_nhwc_pair -- two independent convolutions y0 = conv3x3(x0, w0), y1 = conv3x3(x1, w1) (stride 1, zero padding 1, no bias,
+ * no activation, no residual operands) with common in_channels and out_channels in ONE persistent launch: scratch.layer3_rn and
+ * layer4_rn of the DPT decoders (dmidas/blocks.py:64-80, both 1024 -> 256 at the large backbones).  A launch below one round of
+ * tiles costs one tile's K loop whatever its size; the walk covers the tile list of the first followed by the tile list of the
+ * second (image geometry, operand bases and output base switch per tile), so two launches that fit one round together cost one.
+ * Every output element keeps its accumulation chain: both results are BIT-IDENTICAL to two ds_conv3x3_nhwc calls.
+ *   x_i [batch_i, height_i, width_i, in_channels] NHWC   w_i [out_channels, 3, 3, in_channels]
+ *   y_i [batch_i * height_i * width_i + 1, out_channels]: the NHWC result followed by ONE dummy row, which receives the rows of a
+ *       partial tile beyond the image (a constant store count per tile); an image may have fewer than 256 pixels
+ * in_channels % 128 == 0 (<= 4096), out_channels % 256 == 0, every pointer 16-byte aligned, dtype f16 or bf16; else DS_EINVAL.
+ * Timer: DS_KT_CONV3X3 (one launch).
+ */
+int ds_conv3x3_nhwc_pair(ds_ctx *ctx, const void *x0, const void *w0, void *y0, int batch0, int height0, int width0,
+                         const void *x1, const void *w1, void *y1, int batch1, int height1, int width1,
+                         int in_channels, int out_channels, int dtype, void *stream);
+
+/*
+ * ds_linear_rows4 --up to four small GEMMs with common shape in ONE launch:
+ *     y_p[r, :] = x_p[r, :] . w_p^T + bias_p,   r < rows,  p < count <= 4
+ * The cls halves of the four read-out projections above (cls_vec of ds_linear_readout): x_p is row 0 of every image of a padded tap,
+ * read in place -- row r of problem p starts x_row_pitch ELEMENTS behind row r - 1 (tokens_padded * in_features there), so no
+ * gather, no zero padding to a 256-row tile and no concatenation precede the launch.  The pointer sets travel by value in the kernel
+ * arguments: no device-side table, no allocation, no synchronisation; the launch can be captured into a hipGraph.
+ *   x_p [rows rows of in_features, x_row_pitch apart]   w_p [out_features, in_features]   bias_p [out_features] or NULL
+ *   y_p [rows, out_features] contiguous
+ * Every output element runs the accumulation chain of ds_linear: the result is BIT-IDENTICAL to ds_linear on the same rows gathered
+ * and zero-padded to 256.  Rows beyond `rows` inside the last 32-row block are neither read outside x nor stored.
+ * out_features % 64 == 0, in_features % 128 == 0 (128 .. 16384), rows 1 .. 65536, x_row_pitch >= in_features, % 8 == 0 and < 2^25,
+ * every pointer 16-byte aligned, dtype f16 or bf16; anything else DS_EINVAL.  Timer: DS_KT_LINEAR.  No counterpart in the reference
+ * (it concatenates the cls token to every token and runs one Linear(2C -> C): dmidas/backbones/utils.py:28-39).
+ */
+typedef struct ds_rows_problem {
+    const void *x;
+    int64_t x_row_pitch;
+    const void *w;
+    const void *bias;
+    void *y;
+} ds_rows_problem;
+int ds_linear_rows4(ds_ctx *ctx, const ds_rows_problem *problems, int count, int64_t rows, int64_t out_features,
+                    int64_t in_features, int dtype, void *stream);
+
+/*
  * LayerNorm folded into the Linear behind it -- the norm1 -> qkv and norm2 -> fc1 pairs of every encoder block (timm's Block as run
  * by dmidas/backbones/beit.py:94-107: `x + gamma_1 * attn(norm1(x))`, `x + gamma_2 * mlp(norm2(x))`; ddepth_anything_v2/
  * depth_anything_v2/dinov2_layers/block.py:82-107).  With W' = W . diag(ln_weight), colsum[n] = sum_k W'[n][k] (of the rounded

@@ -140,6 +140,11 @@ struct LinParams {
     const void *x1, *w1;
     void *y1;
     int seg_t0, M1, nbm1, nbn1;
+    // VT 5 (two-segment tile list of two 3 x 3 convolutions, ds_conv3x3_nhwc_pair): positions [0, seg_t0) are the tiles of the convolution
+    // described by the fields above, positions seg_t0 .. those of a second one with the same C and N -- image x1 [M1 / (H1 W1), H1, W1, C],
+    // weights w1, output y1 (nbm1 row panels).  M and M1 need not reach 256: rows >= M / M1 of a tile read the zero line and are
+    // stored to the DUMMY row M / M1 behind the segment's output (a constant store count per tile)
+    int H1, W1;
 };
 // The kernels take LinParams by value as their ONLY argument, so it sits at the start of the kernel-argument segment.  VT 4 reads the
 // fields of its second segment through this pointer, made opaque at every use: they are then fetched per tile (scalar loads of the
@@ -295,6 +300,10 @@ template <int N> __device__ __forceinline__ void ln_wait_vm() { asm volatile("s_
 // and the store map follow the segment in the epilogue.  K loop, LDS map, DMA schedule and every counted wait are untouched: a tile of
 // either segment issues NBIAS bias loads (segment 1: the null-bias dummy) and 16 stores.  An output element keeps its accumulation
 // chain, so both results are bit-identical to the two separate launches.
+// VT = 5 (CONV 1, no bias / activation / residuals): the same walk over the tile lists of TWO convolutions with common C and N
+// (LinParams: seg_t0, x1, w1, y1, M1, nbm1, H1, W1) -- scratch.layer3_rn + layer4_rn, each a part of one round on its own.  set_tile
+// takes the segment's M, H, W and bases from the kernel arguments, forms okA from them and keeps the segment's W for LN_STAGE's row
+// step; rows of a partial tile behind the segment's last pixel read the zero line and are stored to the dummy row behind its output.
 template <int BF16, int EPI, int CONV, int RES, int VT = 0, int NH = 0>
 __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
 {
@@ -335,7 +344,9 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
     // its XCD's range).  Per tile: origin, operand bases and (CONV) the border bits of this thread's four pixels.
     static_assert(VT != 4 || (EPI == 0 && CONV == 0 && RES == 0 && NH == 0), "the two-segment tile list is built for the plain dense epilogue");
     int bm0 = 0, bn0 = 0;
-    int seg = 0;            // VT 4: the segment of the tile list the current tile belongs to (workgroup-uniform)
+    static_assert(VT != 5 || (EPI == 0 && CONV == 1 && RES == 0 && NH == 0), "the convolution pair is built for the plain zero-padded convolution");
+    int seg = 0;            // VT 4 / 5: the segment of the tile list the current tile belongs to (workgroup-uniform)
+    int curW = 0;           // VT 5: image width of the current tile's segment (LN_STAGE's row step)
     const unsigned char *xb = nullptr, *wb = nullptr;
     unsigned okA = 0;       // CONV: bit 6*(2h+i) + t (t = 0..2): row y-1+t of this piece's pixel is inside the image; + 3 + t: column x-1+t
     auto set_tile = [&](const int orig) {
@@ -355,6 +366,30 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
                 wb = (const unsigned char *)pk->w1 + (size_t)bn0 * K * sizeof(T);
                 return;
             }
+        }
+        if constexpr (VT == 5) {
+            // the segment's geometry and operand bases through the kernel-argument pointer, as VT 4: fetched per tile, not kept live
+            const LinParamsK pk = ln_kernarg();
+            const int t0 = pk->seg_t0;
+            seg = tile >= t0 ? 1 : 0;
+            const int ms = seg ? pk->M1 : pk->M, hs = seg ? pk->H1 : pk->H, ws = seg ? pk->W1 : pk->W;
+            ln_tile_origin(seg ? pk->nbm1 : pk->nbm, pk->nbn, ms, 256, tile - (seg ? t0 : 0), bm0, bn0);
+            bm0 = max(bm0, 0);                                               // a segment of fewer than 256 pixels: one partial tile
+            xb = (const unsigned char *)(seg ? pk->x1 : pk->x) + (size_t)bm0 * rowbytes;
+            wb = (const unsigned char *)(seg ? pk->w1 : pk->w) + (size_t)bn0 * K * sizeof(T);
+            curW = ws;
+            okA = 0;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const unsigned row = (unsigned)(bm0 + rowA[i] + 64 * h);
+                    const unsigned pix = row % (unsigned)(hs * ws);
+                    const int py = (int)(pix / (unsigned)ws), px = (int)(pix % (unsigned)ws);
+                    const unsigned bits = (py > 0 ? 1u : 0u) | 2u | (py < hs - 1 ? 4u : 0u) | (px > 0 ? 8u : 0u) | 16u | (px < ws - 1 ? 32u : 0u);
+                    okA |= (row < (unsigned)ms ? bits : 0u) << (6 * (2 * h + i));      // rows behind the segment: every tap from the zero line
+                }
+            return;
         }
         ln_tile_origin(P, tile, bm0, bn0);
         xb = (const unsigned char *)P.x + (size_t)bm0 * rowbytes;
@@ -383,7 +418,7 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
         if (CONV) {              /* K-tile kt = tap kt % 9 of channel chunk kt / 9: the nine taps of one 64-channel chunk */ \
             const int cc_ = ((kt) * 7282) >> 16, tap_ = (kt) - 9 * cc_;      /* follow each other, their pixels stay in L2 */ \
             dy_ = ((tap_ * 11) >> 5) - 1; dx_ = tap_ - 3 * (dy_ + 1) - 1;                                                \
-            aoff_ = cc_ * 128 + (dy_ * P.W + dx_) * rowbytes;                                                            \
+            aoff_ = cc_ * 128 + (dy_ * (VT == 5 ? curW : P.W) + dx_) * rowbytes;                                         \
             koff_ = (unsigned)(tap_ * P.cpt + cc_) * 128u;               /* the weights stay [out][tap][in] */             \
             if (CONV >= 3) { wrapy_ = -(long)dy_ * ((long)P.H * P.W * rowbytes); wrapx_ = -(long)dx_ * ((long)P.W * rowbytes); } \
         }                                                                                                                \
@@ -657,7 +692,7 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
     // (early mode runs set_tile(next) BEFORE the epilogue: everything the epilogue reads per tile is captured here -- the origin, and for
     // VT 4 the segment, which decides the output base and the store map; the null-bias decision is taken right here)
     const int cbm0 = bm0, cbn0 = bn0;
-    const bool cseg = VT == 4 && seg != 0;
+    const bool cseg = (VT == 4 || VT == 5) && seg != 0;
     const int next = orig + (int)gridDim.x;
     // (VT 4: the lane index the epilogue forms its rows and columns from is made opaque HERE, per tile.  With two store maps the
     // loop-invariant per-lane address parts of BOTH would otherwise be hoisted out of the tile loop and kept in registers across the
@@ -677,12 +712,20 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear256(LinParams P)
             s1_np = (unsigned)pk->vt_np; s1_c = (unsigned)pk->vt_c; s1_magic = pk->vt_magic;
         }
     }
+    int s1_rows = 0;                                            // VT 5: rows of the tile's segment
+    if constexpr (VT == 5) {
+        const LinParamsK pk = ln_kernarg();
+        yb = (T *)(cseg ? pk->y1 : pk->y);
+        s1_rows = cseg ? pk->M1 : pk->M;
+    }
     // element offset of the 8 outputs (row, col .. col + 7) of this tile; o0 = their offset in a row-major y
     auto tile_out_off = [&](const int row, const int col, const size_t o0) -> size_t {
         if constexpr (VT == 4) {
             if (!cseg) return o0;
             const unsigned b = __umulhi((unsigned)col, s1_magic), n = (unsigned)col - b * s1_np;
             return ((size_t)b * s1_c + row) * (size_t)s1_np + n;
+        } else if constexpr (VT == 5) {
+            return row < s1_rows ? o0 : (size_t)s1_rows * P.ldy + col;       // rows behind the segment: its dummy row
         } else return VT ? ln_out_off<VT>(P, row, col) : o0;
     };
     // (CONV 3 / 4: the base stays a scalar HERE, so that the per-lane store address is formed per tile instead of being hoisted out
@@ -1319,9 +1362,6 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear_thin(LinParams P)
         TH_STEP(fa1, fb1, fa0, fb0, st + 1);
     }
     if (st < nst) TH_STEP(fa0, fb0, fa1, fb1, st);
-#undef TH_STEP
-#undef TH_READ
-#undef TH_STAGE
     LN_WAIT_VM(0);                                       // the trailing re-loads: nothing may still be writing LDS at exit
     if (!mw) return;
 
@@ -1360,6 +1400,119 @@ __global__ __launch_bounds__(LN_THREADS) void k_linear_thin(LinParams P)
         *(V8 *)(yb + off) = o;
     }
 }
+
+// ---- up to four thin GEMMs in one launch (ds_linear_rows4) ----------------------------------------------------------------------
+// The cls halves of the four read-out projections: y_p = x_p . w_p^T + b_p for p < 4, a few dozen rows each (one per image), common
+// rows / N / K.  One launch of k_linear_thin's piece loop (the macros above, unchanged: 32 rows x 64 columns per piece, two K-tiles per
+// step, the accumulation chain of the main kernel), the problem index as blockIdx.y.  The four pointer sets travel by value in the
+// kernel arguments and are read per workgroup through the kernel-argument pointer (scalar loads at a uniform index: no device-side
+// table, nothing to allocate or synchronise, so the launch can be captured into a hipGraph).  Row r of problem p starts at
+// x_p + r * pitch_p bytes -- row 0 of image r inside the padded tap, read where it lies.  Rows of the last 32-row block beyond `rows`
+// stage the last valid row a second time (never an address outside x) and are not stored.
+struct LinRows4 {
+    const void *x[4], *w[4], *bias[4];
+    void *y[4];
+    long long pitch[4];         // bytes between consecutive rows of x_p
+    int rows, N, K;
+};
+template <int BF16>
+__global__ __launch_bounds__(LN_THREADS) void k_linear_rows4(LinRows4 P)
+{
+    typedef ln_traits<BF16> TR;
+    typedef typename TR::T T;
+    typedef typename TR::V8 V8;
+    constexpr int S = 6;
+    extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const __attribute__((address_space(4))) LinRows4 *pk = (const __attribute__((address_space(4))) LinRows4 *)__builtin_amdgcn_kernarg_segment_ptr();
+    const int prob = (int)blockIdx.y;
+    const int ncb = P.N >> 6;                            // pieces per row block
+    const int rb = (int)blockIdx.x / ncb, cbk = (int)blockIdx.x - rb * ncb;
+    const int row0 = 32 * rb, col0 = cbk * 64, rows = P.rows;
+    const int K = P.K, nst = K >> 7;                     // steps of two K-tiles
+    const unsigned rowbytes = (unsigned)K * (unsigned)sizeof(T);
+    const unsigned pitch = (unsigned)pk->pitch[prob];    // 31 * pitch < 2^31 (host)
+    // staging as in k_linear_thin; the x row of LDS row j is row min(row0 + j, rows - 1) of the problem
+    unsigned srcA, srcB[2];
+    {
+        const int j = 8 * (wid & 3) + (lane >> 3);
+        const int jr = min(row0 + j, rows - 1) - row0;
+        srcA = (unsigned)jr * pitch + (unsigned)(((lane & 7) ^ ((j >> 1) & 7)) << 4) + (unsigned)(wid >> 2) * 128u;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int j = 8 * ((2 * wid + i) & 7) + (lane >> 3);
+        srcB[i] = (unsigned)j * rowbytes + (unsigned)(((lane & 7) ^ ((j >> 1) & 7)) << 4) + (unsigned)(wid >> 2) * 128u;
+    }
+    const unsigned char *xb = (const unsigned char *)pk->x[prob] + (size_t)row0 * pitch;
+    const unsigned char *wb = (const unsigned char *)pk->w[prob] + (size_t)col0 * rowbytes;
+    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void *)lds;
+    const bool mw = wid < 2;
+    unsigned offA[8], offB[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int j = u >> 2, ks = u & 3;
+        const unsigned sl = (unsigned)((LN_MF16 ? 4 * (ks >> 1) + (lane >> 4) : 2 * ks + hi) ^ ((lane >> 1) & 7)) << 4;
+        const int lrow = LN_MF16 ? 16 * (ks & 1) + (lane & 15) : l31;
+        offA[u] = (unsigned)j * 4096u + (unsigned)lrow * 128u + sl;
+        offB[u] = 8192u + (unsigned)j * 8192u + (unsigned)((wid & 1) * 32 + lrow) * 128u + sl;
+    }
+    LN_SMALL_ACC(mine);
+    const int e_row = row0 + LN_SMALL_ROW;
+    const int e_cb = col0 + (wid & 1) * 32 + LN_SMALL_COL;
+    const T *bias = (const T *)pk->bias[prob];
+    V8 e_bv[2];
+    if (mw && bias) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) e_bv[k] = *(const V8 *)(bias + e_cb + LN_SMALL_DCOL(k));
+    }
+#pragma unroll
+    for (int t = 0; t < S - 1; ++t) TH_STAGE(t);
+    V8 fa0[8], fb0[8], fa1[8], fb1[8];
+    LN_WAIT_VM(12);
+    LN_BARRIER();
+    if (mw) {
+        TH_READ(fa0, fb0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        LN_WAIT_LGKM0();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    int st = 0;
+    for (; st + 1 < nst; st += 2) {
+        TH_STEP(fa0, fb0, fa1, fb1, st);
+        TH_STEP(fa1, fb1, fa0, fb0, st + 1);
+    }
+    if (st < nst) TH_STEP(fa0, fb0, fa1, fb1, st);
+    LN_WAIT_VM(0);
+    if (!mw) return;
+
+    // ---- epilogue of this wave's 32 x 32 block: k_linear_thin's with EPI 0 / RES 0, rows >= `rows` dropped
+    T *yb = (T *)pk->y[prob];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int row = e_row + LN_SMALL_DROW(k), col = e_cb + LN_SMALL_DCOL(k);
+        V8 bv;
+        if (bias) bv = e_bv[k];
+        else {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) bv[t] = (T)0.f;
+        }
+        float v[8];
+        LN_SMALL_V(v, mine, k);
+        V8 o;
+#pragma unroll
+        for (int t = 0; t < 8; t += 2) {
+            const lf32x2 u = {v[t] + (float)bv[t], v[t + 1] + (float)bv[t + 1]};
+            o[t] = (T)u[0];
+            o[t + 1] = (T)u[1];
+        }
+        if (row < rows) *(V8 *)(yb + (size_t)row * P.N + col) = o;
+    }
+}
+#undef TH_STEP
+#undef TH_READ
+#undef TH_STAGE
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------
 // A/B switches of the GEMM path, read from the environment ONCE (hundreds of launches per forward; ds_linear_reload_env re-reads
@@ -1739,6 +1892,79 @@ DS_API int ds_conv3x3_nhwc_circular(ds_ctx *ctx, const void *x, const void *w, c
     return ln_conv3x3<1>("ds_conv3x3_nhwc_circular", ctx, x, w, bias, res1, res2, y, batch, height, width, in_channels, out_channels, act, dtype, stream);
 }
 
+// Two independent zero-padded 3 x 3 convolutions with common C and N (no bias, no activation, no residuals: scratch.layer3_rn and
+// layer4_rn of the DPT decoders, dmidas/blocks.py:64-80) as ONE persistent walk over both tile lists (k_linear256<.., VT 5>).  A launch
+// below one round of tiles costs one tile's K loop whatever its size, so two such launches that fit one round together cost one.
+template <int BF16>
+static int ln_launch_conv_pair(ds_ctx *ctx, const LinParams &P0, hipStream_t stream)
+{
+    static std::atomic<uint64_t> attr_done{0};
+    auto fn = k_linear256<BF16, 0, 1, 0, 5>;
+    DS_HIP_CHECK(hipSetDevice(ctx->device));
+    const uint64_t bit = 1ull << (ctx->device & 63);
+    if (!(attr_done.load(std::memory_order_relaxed) & bit)) {
+        DS_HIP_CHECK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, LN_LDS_BYTES));
+        attr_done.fetch_or(bit, std::memory_order_relaxed);
+    }
+    if (!ctx->ncu) {
+        int ncu = 0;
+        DS_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+        ctx->ncu = ncu >= 8 ? ncu / 8 * 8 : 8;
+    }
+    const LinOptions &O = ln_options();
+    int grid = ctx->ncu;
+    if (O.grid >= 8) grid = O.grid / 8 * 8;
+    LinParams P = P0;
+    P.bnw = 256;
+    P.early = O.early;
+    P.n_main = P.seg_t0 + P.nbm1 * P.nbn;
+    const int kt0 = ds_kt_begin(ctx, DS_KT_CONV3X3, stream);
+    hipLaunchKernelGGL(fn, dim3(P.n_main < grid ? P.n_main : grid), dim3(LN_THREADS), LN_LDS_BYTES, stream, P);
+    ds_kt_end(ctx, DS_KT_CONV3X3, kt0, stream);
+    DS_HIP_CHECK(hipGetLastError());
+    return DS_OK;
+}
+
+DS_API int ds_conv3x3_nhwc_pair(ds_ctx *ctx, const void *x0, const void *w0, void *y0, int batch0, int height0, int width0,
+                                const void *x1, const void *w1, void *y1, int batch1, int height1, int width1,
+                                int in_channels, int out_channels, int dtype, void *stream)
+{
+    const char *NAME = "ds_conv3x3_nhwc_pair";
+    DS_REQUIRE(ctx && x0 && w0 && y0 && x1 && w1 && y1, DS_EINVAL, "%s: null argument", NAME);
+    DS_REQUIRE(batch0 > 0 && height0 > 0 && width0 > 0 && height0 < 32768 && width0 < 32768 &&
+               batch1 > 0 && height1 > 0 && width1 > 0 && height1 < 32768 && width1 < 32768, DS_EINVAL, "%s: bad image shape", NAME);
+    const int64_t m0 = (int64_t)batch0 * height0 * width0, m1 = (int64_t)batch1 * height1 * width1;
+    DS_REQUIRE(m0 < (1ll << 31) - 256 && m1 < (1ll << 31) - 256 && (m0 + 255) / 256 + (m1 + 255) / 256 < (1ll << 20), DS_EINVAL,
+               "%s: too many pixels", NAME);
+    DS_REQUIRE(in_channels >= 64 && in_channels % 64 == 0 && (9 * in_channels / 64) % 2 == 0 && in_channels <= 4096, DS_EINVAL,
+               "%s: in_channels must be a multiple of 128 (<= 4096)", NAME);
+    DS_REQUIRE(out_channels > 0 && out_channels % 256 == 0, DS_EINVAL, "%s: out_channels must be a multiple of 256", NAME);
+    DS_REQUIRE(dtype == DS_DTYPE_F16 || dtype == DS_DTYPE_BF16, DS_EINVAL, "%s: dtype must be f16 or bf16", NAME);
+    DS_REQUIRE((((uintptr_t)x0 | (uintptr_t)w0 | (uintptr_t)y0 | (uintptr_t)x1 | (uintptr_t)w1 | (uintptr_t)y1) & 15) == 0, DS_EINVAL,
+               "%s: every pointer must be 16-byte aligned", NAME);
+    int rc = ds_ctx_reserve(ctx, &ctx->zero_line, &ctx->zero_line_bytes, 256);
+    if (rc != DS_OK) return rc;
+    if (!ctx->zero_line_cleared) {
+        DS_HIP_CHECK(hipMemsetAsync(ctx->zero_line, 0, 256, (hipStream_t)stream));
+        DS_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+        ctx->zero_line_cleared = 1;
+    }
+    LinParams P;
+    memset(&P, 0, sizeof(P));
+    P.x = x0; P.w = w0; P.y = y0; P.zeros = ctx->zero_line;
+    P.M = (int)m0; P.N = out_channels; P.K = 9 * in_channels;
+    P.nbm = (int)((m0 + 255) / 256); P.nbn = out_channels / 256;
+    P.H = height0; P.W = width0; P.C = in_channels; P.cpt = in_channels / 64; P.magic = 65536 / P.cpt + 1;
+    for (int kt = 0; kt < P.K / 64; ++kt)
+        DS_REQUIRE(((kt * 7282) >> 16) == kt / 9, DS_EUNSUPPORTED, "%s: K-tile arithmetic does not cover %d channels", NAME, in_channels);
+    P.ldy = out_channels;
+    P.x1 = x1; P.w1 = w1; P.y1 = y1;
+    P.seg_t0 = P.nbm * P.nbn; P.M1 = (int)m1; P.nbm1 = (int)((m1 + 255) / 256); P.nbn1 = P.nbn;
+    P.H1 = height1; P.W1 = width1;
+    P.kt_kind = DS_KT_CONV3X3;
+    return dtype == DS_DTYPE_F16 ? ln_launch_conv_pair<0>(ctx, P, (hipStream_t)stream) : ln_launch_conv_pair<1>(ctx, P, (hipStream_t)stream);
+}
+
 // V^T of an encoder block straight out of the GEMM: vt[b][c][n] = sum_k w_v[c][k] h[b][n][k] (the reference computes
 // qkv = Linear(h) and permutes, dmidas/backbones/beit.py:71-74, dinov2_layers/attention.py:52-55; the attention kernel wants V
 // with the key index contiguous).  The GEMM runs with W_v as the row operand and ALL tokens of the batch as columns; the
@@ -1876,6 +2102,56 @@ DS_API int ds_linear_readout(ds_ctx *ctx, const void *x, const void *w_tok, cons
     P.kt_kind = DS_KT_LINEAR_READOUT;
     hipStream_t st = (hipStream_t)stream;
     return dtype == DS_DTYPE_F16 ? ln_launch<0, 1, 0, 1, 3>(ctx, P, st) : ln_launch<1, 1, 0, 1, 3>(ctx, P, st);
+}
+
+// Up to four thin GEMMs y_p = x_p . w_p^T + bias_p with common rows / out_features / in_features in ONE launch (k_linear_rows4): the
+// cls vectors of the four read-outs, whose x rows are row 0 of every image of a padded tap (x_row_pitch = tokens_padded * in_features
+// elements).  Values: the accumulation chain of k_linear256, i.e. what ds_linear gives on the same rows padded to a 256-row tile.
+template <int BF16>
+static int ln_launch_rows4(ds_ctx *ctx, const LinRows4 &P, int count, hipStream_t stream)
+{
+    static std::atomic<uint64_t> attr_done{0};
+    auto fn = k_linear_rows4<BF16>;
+    DS_HIP_CHECK(hipSetDevice(ctx->device));
+    const uint64_t bit = 1ull << (ctx->device & 63);
+    if (!(attr_done.load(std::memory_order_relaxed) & bit)) {
+        DS_HIP_CHECK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 6 * RG_SLOT));
+        attr_done.fetch_or(bit, std::memory_order_relaxed);
+    }
+    const int kt0 = ds_kt_begin(ctx, DS_KT_LINEAR, stream);
+    hipLaunchKernelGGL(fn, dim3((unsigned)((P.rows + 31) / 32 * (P.N / 64)), (unsigned)count), dim3(LN_THREADS), 6 * RG_SLOT, stream, P);
+    ds_kt_end(ctx, DS_KT_LINEAR, kt0, stream);
+    DS_HIP_CHECK(hipGetLastError());
+    return DS_OK;
+}
+
+DS_API int ds_linear_rows4(ds_ctx *ctx, const ds_rows_problem *problems, int count, int64_t rows, int64_t out_features,
+                           int64_t in_features, int dtype, void *stream)
+{
+    DS_REQUIRE(ctx && problems, DS_EINVAL, "ds_linear_rows4: null argument");
+    DS_REQUIRE(count >= 1 && count <= 4, DS_EINVAL, "ds_linear_rows4: count must be 1 .. 4");
+    DS_REQUIRE(rows >= 1 && rows <= 65536, DS_EINVAL, "ds_linear_rows4: rows must be 1 .. 65536");
+    DS_REQUIRE(out_features > 0 && out_features % 64 == 0 && out_features <= 65536, DS_EINVAL,
+               "ds_linear_rows4: out_features must be a multiple of 64 (<= 65536)");
+    DS_REQUIRE(in_features >= 128 && in_features % 128 == 0 && in_features <= 16384, DS_EINVAL,
+               "ds_linear_rows4: in_features must be a multiple of 128 (<= 16384)");
+    DS_REQUIRE(dtype == DS_DTYPE_F16 || dtype == DS_DTYPE_BF16, DS_EINVAL, "ds_linear_rows4: dtype must be f16 or bf16");
+    DS_REQUIRE((rows + 31) / 32 * (out_features / 64) < (1ll << 31), DS_EINVAL, "ds_linear_rows4: too many pieces for one grid");
+    LinRows4 P;
+    memset(&P, 0, sizeof(P));
+    for (int p = 0; p < count; ++p) {
+        const ds_rows_problem &q = problems[p];
+        DS_REQUIRE(q.x && q.w && q.y, DS_EINVAL, "ds_linear_rows4: null x, w or y");
+        DS_REQUIRE(((uintptr_t)q.x & 15) == 0 && ((uintptr_t)q.w & 15) == 0 && ((uintptr_t)q.y & 15) == 0 && ((uintptr_t)q.bias & 15) == 0, DS_EINVAL,
+                   "ds_linear_rows4: x, w (the LDS-DMA sources), y and bias must be 16-byte aligned");
+        // the per-lane DMA offset inside a 32-row block is 32 bits: 31 row pitches + one row
+        DS_REQUIRE(q.x_row_pitch >= in_features && q.x_row_pitch % 8 == 0 && q.x_row_pitch * 2 * 32 < (1ll << 31), DS_EINVAL,
+                   "ds_linear_rows4: x_row_pitch must be >= in_features, a multiple of 8 elements and below 2^25 elements");
+        P.x[p] = q.x; P.w[p] = q.w; P.bias[p] = q.bias; P.y[p] = q.y;
+        P.pitch[p] = q.x_row_pitch * 2;
+    }
+    P.rows = (int)rows; P.N = (int)out_features; P.K = (int)in_features;
+    return dtype == DS_DTYPE_F16 ? ln_launch_rows4<0>(ctx, P, count, (hipStream_t)stream) : ln_launch_rows4<1>(ctx, P, count, (hipStream_t)stream);
 }
 
 // LayerNorm folded into the Linear that follows it (the norm1 -> qkv and norm2 -> fc1 pairs of every encoder block: timm's Block as

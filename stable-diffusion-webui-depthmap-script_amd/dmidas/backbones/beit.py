@@ -263,14 +263,23 @@ class ProjectReadout(nn.Module):       # utils.py:28-39
             return _native.reassemble_readout(proj, clsvec)
         return F.gelu(proj[:, 1:] + clsvec[:, None])
 
-    def forward_padded(self, xp, n_valid):
+    def takes_hip_route(self, xp):
+        """forward_padded runs ds_linear_readout on this padded tap."""
+        from src import _native
+        w_tok = self._split()[0]
+        return (self.start_index == 1 and vm.READOUT_HIP and vm.LINEAR_HIP == "all" and vm.half_on_gpu(xp) and xp.is_contiguous()
+                and _native.linear_readout_supported(xp, w_tok) and vm.hip_gemm_ok(xp.shape[0] * xp.shape[1], w_tok.shape[0]))
+
+    def forward_padded(self, xp, n_valid, clsvec=None):
         """The same on the PADDED block output [B, Np, C] the encoder leaves behind (contiguous: no copy of the tap, which a
         library GEMM on the sliced view x[:, :n_valid] makes): ONE in-tree GEMM whose epilogue adds the per-image cls vector,
-        applies the exact GELU, drops the cls / pad rows and leaves the tokens NHWC (ds_linear_readout).  -> [B, N-1, C]."""
+        applies the exact GELU, drops the cls / pad rows and leaves the tokens NHWC (ds_linear_readout).  -> [B, N-1, C].
+        clsvec: the cls half of the projection, when the caller has it already (cls_vectors4)."""
         from src import _native
         w_tok, w_cls = self._split()
-        if (self.start_index == 1 and vm.READOUT_HIP and vm.LINEAR_HIP == "all" and vm.half_on_gpu(xp) and xp.is_contiguous()
-                and _native.linear_readout_supported(xp, w_tok) and vm.hip_gemm_ok(xp.shape[0] * xp.shape[1], w_tok.shape[0])):
+        if self.takes_hip_route(xp):
+            if clsvec is not None:
+                return _native.linear_readout(xp, n_valid, w_tok, clsvec)
             # [B, C]: the cls half of the projection.  In-tree as well (rows padded to one 256-row tile): a library GEMM picks its
             # kernel -- and its summation order -- by the batch size, and the same image would come out differently at batch 8 and 32
             x0 = xp[:, 0].contiguous()
@@ -280,6 +289,20 @@ class ProjectReadout(nn.Module):       # utils.py:28-39
                 clsvec = F.linear(x0, w_cls, self.project[0].bias)
             return _native.linear_readout(xp, n_valid, w_tok, clsvec)
         return self.forward(xp[:, :n_valid])
+
+
+def cls_vectors4(readouts, taps):
+    """The cls halves W_cls . x[:, 0] + b of up to four read-outs in ONE launch that reads the cls rows where they lie in the padded
+    taps (ds_linear_rows4), when every read-out takes the HIP route on its tap and the in-tree GEMM is the rule for the cls half
+    (vm.invariant()); else a list of None: every ProjectReadout.forward_padded then computes its own.  The same bits either way."""
+    from src import _native
+    none = [None] * len(taps)
+    if not (vm.READOUT_CLS4 and vm.invariant() and 1 <= len(taps) <= 4 and all(r.takes_hip_route(t) for r, t in zip(readouts, taps))):
+        return none
+    w_cls = [r._split()[1] for r in readouts]
+    if not (all(_native.linear_supported(t[:, 0], w) for t, w in zip(taps, w_cls)) and _native.linear_rows4_supported(taps, w_cls)):
+        return none
+    return _native.linear_rows4(taps, w_cls, [r.project[0].bias for r in readouts])
 
 
 class _Skip(nn.Module):                 # placeholder for Transpose / Unflatten slots (no parameters) so indices match
@@ -314,8 +337,10 @@ class BeitBackbone(nn.Module):
         else:
             taps, grid, n_valid = self.model.forward_taps(x, self.hooks, padded=True)
         outs = []
-        for tap, post in zip(taps, (self.act_postprocess1, self.act_postprocess2, self.act_postprocess3, self.act_postprocess4)):
-            y = post[0].forward_padded(tap, n_valid)           # ProjectReadout: [B, N-1, C]
+        posts = (self.act_postprocess1, self.act_postprocess2, self.act_postprocess3, self.act_postprocess4)
+        clsvecs = cls_vectors4([post[0] for post in posts], taps)
+        for tap, post, clsvec in zip(taps, posts, clsvecs):
+            y = post[0].forward_padded(tap, n_valid, clsvec)   # ProjectReadout: [B, N-1, C]
             y = y.reshape(y.shape[0], grid[0], grid[1], y.shape[2]).permute(0, 3, 1, 2)     # NHWC view, no copy
             for layer in list(post)[3:]:
                 y = vm.conv_module(layer, y)                    # library convolution + in-tree bias pass

@@ -20,7 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from src import vit_mi355x as vm
-from .beit import ProjectReadout, _Skip
+from .beit import ProjectReadout, _Skip, cls_vectors4
 
 
 # ---- ResNetV2 stem (timm/models/resnetv2.py, preact=False, stem_type='same', StdConv2dSame eps=1e-8, GroupNorm 32) -------
@@ -295,8 +295,9 @@ class VitBackbone(nn.Module):
         stage_outs, taps, grid, n_valid = self.model.forward_taps(x, self.hooks, self.number_stages)
         posts = (self.act_postprocess1, self.act_postprocess2, self.act_postprocess3, self.act_postprocess4)
         outs = list(stage_outs)
-        for tap, post in zip(taps, posts[self.number_stages:]):
-            y = post[0].forward_padded(tap, n_valid)           # ProjectReadout on the padded block output
+        clsvecs = cls_vectors4([post[0] for post in posts[self.number_stages:]], taps)
+        for tap, post, clsvec in zip(taps, posts[self.number_stages:], clsvecs):
+            y = post[0].forward_padded(tap, n_valid, clsvec)   # ProjectReadout on the padded block output
             y = y.reshape(y.shape[0], grid[0], grid[1], y.shape[2]).permute(0, 3, 1, 2)      # NHWC view, no copy
             for layer in list(post)[3:]:
                 y = vm.conv_module(layer, y)

@@ -23,7 +23,7 @@ EXPORTS = [
     "ds_version", "ds_last_error", "ds_normalmap_f64", "ds_normalmap_gradient_f32", "ds_reassemble_readout", "ds_bias_act_nhwc", "ds_linear", "ds_linear_residual", "ds_linear_vt", "ds_linear_qkv", "ds_conv3x3_nhwc", "ds_ctx_create", "ds_ctx_destroy", "ds_stereo_warp", "ds_depth_minmax",
     "ds_stereo_last_exact_rows", "ds_copy_view", "ds_overlap_red_cyan", "ds_normalmap", "ds_depth_to_u16",
     "ds_convert_to_i16", "ds_profile_enable", "ds_profile_last_ms", "ds_stereo_last_stats", "ds_attention_fwd", "ds_attention_bias_pack", "ds_colorize_u16", "ds_residual_layernorm", "ds_boost_blend", "ds_upsample_bilinear_nhwc", "ds_dpt_head_tail", "ds_preprocess_bicubic", "ds_linear_reload_env", "ds_attention_reload_env", "ds_normalmap_selfcheck", "ds_normalmap_gradient_f16", "ds_normalmap_gradient_blur_f32",
-    "ds_linear_shuffle", "ds_linear_readout", "ds_kernel_timer_enable", "ds_kernel_timer_read", "ds_kernel_timer_read_each", "ds_group_norm_nchw",
+    "ds_linear_shuffle", "ds_linear_readout", "ds_linear_rows4", "ds_conv3x3_nhwc_pair", "ds_kernel_timer_enable", "ds_kernel_timer_read", "ds_kernel_timer_read_each", "ds_group_norm_nchw",
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
@@ -34,6 +34,11 @@ EXPORTS = [
 
 class DepthStereoError(RuntimeError):
     pass
+
+
+class ds_rows_problem(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_void_p), ("x_row_pitch", ctypes.c_int64), ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+                ("y", ctypes.c_void_p)]
 
 
 class ds_eye(ctypes.Structure):
@@ -48,6 +53,7 @@ _lib_lock = threading.Lock()
 # really took the in-tree kernels it claims: a routing threshold that silently sends a shape to the library shows up here).
 # ds_linear_qkv runs two of the counted GEMMs in one launch: it counts under its own name AND once under ds_linear and ds_linear_vt,
 # so "how many Q/K and V^T GEMMs ran in-tree" reads the same on either route; ds_linear_qkv alone tells the routes apart.
+# ds_linear_rows4 likewise: its own name once, and ds_linear once per GEMM it carries; ds_conv3x3_nhwc_pair: ds_conv3x3_nhwc twice.
 CALLS = collections.Counter()
 
 
@@ -109,8 +115,10 @@ def lib():
             L.ds_linear_qkv.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, vp]
             L.ds_conv3x3_nhwc.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
             L.ds_conv3x3_nhwc_circular.argtypes = L.ds_conv3x3_nhwc.argtypes
+            L.ds_conv3x3_nhwc_pair.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
             L.ds_linear_shuffle.argtypes = [vp, vp, vp, vp, vp, i64, i64, ci, ci, ci, ci, vp]
             L.ds_linear_readout.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, vp]
+            L.ds_linear_rows4.argtypes = [vp, ctypes.POINTER(ds_rows_problem), ci, i64, i64, i64, ci, vp]
             L.ds_row_stats.argtypes = [vp, vp, vp, i64, ci, ctypes.c_float, ci, vp]
             L.ds_linear_ln.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, ci, ci, vp]
             L.ds_linear_vt_ln.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, ci, vp]
@@ -735,6 +743,44 @@ def linear_readout(x_padded, n_tokens, w_tok, cls_vec):
     return out[:b * (n_tokens - 1)].view(b, n_tokens - 1, n)
 
 
+def linear_rows4_supported(taps, weights):
+    """Shapes ds_linear_rows4 takes: 1 .. 4 contiguous padded taps [B, Np, K] of one shape and dtype, weights [N % 64 == 0, K % 128 == 0]."""
+    t0, w0 = taps[0], weights[0]
+    return (1 <= len(taps) == len(weights) <= 4 and t0.dim() == 3 and 1 <= t0.shape[0] <= 65536
+            and all(t.shape == t0.shape and t.dtype == t0.dtype and t.device == t0.device and t.is_contiguous() for t in taps)
+            and all(w.shape == w0.shape for w in weights) and w0.shape[1] == t0.shape[2] and w0.shape[0] % 64 == 0
+            and w0.shape[1] % 128 == 0 and 128 <= w0.shape[1] <= 16384 and t0.shape[1] * t0.shape[2] < (1 << 25))
+
+
+def linear_rows4(taps, weights, biases, out=None):
+    """[tap[:, 0] @ w.T + b for tap, w, b in zip(taps, weights, biases)] in ONE launch that reads row 0 of every image where it lies in
+    the padded tap (include/depthstereo.h: ds_linear_rows4).  taps: 1 .. 4 contiguous [B, Np, K] float16 / bfloat16 CUDA tensors,
+    weights [N, K], biases [N] or None -> a list of [B, N] (views of `out` [len(taps), B, N] when given: contiguous, the taps' dtype).
+    Bit-identical to linear(tap[:, 0].contiguous(), w, b) per tap."""
+    torch = require_gpu()
+    t0 = taps[0]
+    assert t0.is_cuda and t0.dtype in (torch.float16, torch.bfloat16) and linear_rows4_supported(taps, weights) and len(biases) == len(taps)
+    b, npad, k = t0.shape
+    n = weights[0].shape[0]
+
+    def prep(t):
+        if t is None:
+            return None
+        t = t.detach()
+        return t if (t.dtype == t0.dtype and t.is_contiguous()) else t.to(t0.dtype).contiguous()
+    ws, bs = [prep(w) for w in weights], [prep(v) for v in biases]
+    if out is None:
+        out = torch.empty((len(taps), b, n), dtype=t0.dtype, device=t0.device)
+    assert tuple(out.shape) == (len(taps), b, n) and out.dtype == t0.dtype and out.device == t0.device and out.is_contiguous()
+    probs = (ds_rows_problem * len(taps))()
+    for i, (t, w, v) in enumerate(zip(taps, ws, bs)):
+        probs[i] = ds_rows_problem(t.data_ptr(), npad * k, w.data_ptr(), None if v is None else v.data_ptr(), out[i].data_ptr())
+    CALLS["ds_linear_rows4"] += 1
+    CALLS["ds_linear"] += len(taps)
+    _check(lib().ds_linear_rows4(ctx_for(_dev_index(t0)), probs, len(taps), b, n, k, 1 if t0.dtype == torch.float16 else 2, _stream(t0)))
+    return list(out.unbind(0))
+
+
 def conv_transpose_shuffle_supported(layer, x):
     """ConvTranspose2d layers ds_linear_shuffle takes: kernel == stride (square), no padding / output padding / groups / dilation,
     in_channels % 128 == 0, out_channels % 8 == 0, stride^2 * out_channels % 256 == 0, at least 256 input pixels."""
@@ -1059,16 +1105,7 @@ def conv3x3(conv, x, relu=False, res1=None, res2=None, relu_in=False):
     assert conv3x3_circular_supported(conv, x) if circular else conv3x3_supported(conv, x)
     x = x.contiguous(memory_format=torch.channels_last)
     b, c, h, w = x.shape
-    key = (conv.weight.data_ptr(), conv.weight._version, x.dtype, None if conv.bias is None else conv.bias._version)
-    hit = getattr(conv, "_ds_ohwi", None)
-    if hit is None or hit[0] != key:
-        if hit is not None:
-            from . import vit_mi355x as _vm
-            _vm.cache_evicted()                 # a live hipGraph may still read the old weight image
-        wk = conv.weight.detach().to(x.dtype).permute(0, 2, 3, 1).contiguous()
-        bk = None if conv.bias is None else conv.bias.detach().to(x.dtype).contiguous()
-        hit = conv._ds_ohwi = (key, wk, bk)
-    _, wk, bk = hit
+    wk, bk = _conv_weight_image(conv, x.dtype)
     out = torch.empty((b, conv.out_channels, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     for r in (res1, res2):
         assert r is None or (r.shape == out.shape and r.dtype == x.dtype and r.is_contiguous(memory_format=torch.channels_last))
@@ -1079,6 +1116,55 @@ def conv3x3(conv, x, relu=False, res1=None, res2=None, relu_in=False):
                                 out.data_ptr(), b, h, w, c, conv.out_channels, (2 if relu else 0) | (4 if relu_in else 0),
                                 1 if x.dtype == torch.float16 else 2, _stream(x)))
     return out
+
+
+def _conv_weight_image(conv, dtype):
+    """The cached [out, 3, 3, in] weight image (and bias) of conv3x3, built on first use."""
+    key = (conv.weight.data_ptr(), conv.weight._version, dtype, None if conv.bias is None else conv.bias._version)
+    hit = getattr(conv, "_ds_ohwi", None)
+    if hit is None or hit[0] != key:
+        if hit is not None:
+            from . import vit_mi355x as _vm
+            _vm.cache_evicted()                 # a live hipGraph may still read the old weight image
+        wk = conv.weight.detach().to(dtype).permute(0, 2, 3, 1).contiguous()
+        bk = None if conv.bias is None else conv.bias.detach().to(dtype).contiguous()
+        hit = conv._ds_ohwi = (key, wk, bk)
+    return hit[1], hit[2]
+
+
+def conv3x3_pair_supported(conv0, x0, conv1, x1):
+    """What ds_conv3x3_nhwc_pair takes: two zero-padded 3x3 convolutions without bias, equal in_channels (% 128 == 0) and equal
+    out_channels (% 256 == 0), on two activations of one dtype and device; either may have fewer than 256 pixels."""
+    def one(conv, x):
+        return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1)
+                and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros' and conv.bias is None
+                and x.dim() == 4 and x.shape[1] == conv.in_channels and x.numel() > 0)
+    return (one(conv0, x0) and one(conv1, x1) and conv0.in_channels == conv1.in_channels and conv0.in_channels % 128 == 0
+            and conv0.in_channels <= 4096 and conv0.out_channels == conv1.out_channels and conv0.out_channels % 256 == 0
+            and x0.dtype == x1.dtype and x0.device == x1.device)
+
+
+def conv3x3_pair(conv0, x0, conv1, x1):
+    """(conv0(x0), conv1(x1)) for two bias-free 3x3 convolutions with common in / out channels in ONE persistent launch over both
+    tile lists (include/depthstereo.h: ds_conv3x3_nhwc_pair); channels_last in and out.  Bit-identical to two conv3x3 calls.  Each
+    output is a view of a buffer with one dummy row behind it (the rows of a partial tile beyond the image go there)."""
+    torch = require_gpu()
+    assert x0.is_cuda and x0.dtype in (torch.float16, torch.bfloat16) and conv3x3_pair_supported(conv0, x0, conv1, x1)
+    outs, args, xs = [], [], []
+    for conv, x in ((conv0, x0), (conv1, x1)):
+        x = x.contiguous(memory_format=torch.channels_last)
+        b, c, h, w = x.shape
+        wk, _ = _conv_weight_image(conv, x.dtype)
+        n = conv.out_channels
+        buf = torch.empty((b * h * w + 1, n), dtype=x.dtype, device=x.device)
+        outs.append(buf[:b * h * w].view(b, h, w, n).permute(0, 3, 1, 2))
+        args += [x.data_ptr(), wk.data_ptr(), buf.data_ptr(), b, h, w]
+        xs.append(x)                            # (a channels_last copy lives until the launch is enqueued)
+    CALLS["ds_conv3x3_nhwc_pair"] += 1
+    CALLS["ds_conv3x3_nhwc"] += 2
+    _check(lib().ds_conv3x3_nhwc_pair(ctx_for(_dev_index(x0)), *args, conv0.in_channels, conv0.out_channels,
+                                      1 if x0.dtype == torch.float16 else 2, _stream(x0)))
+    return outs[0], outs[1]
 
 
 def bias_act(x, bias, relu=False, res1=None, res2=None, inplace=True):

@@ -557,6 +557,23 @@ def conv3x3_hip_ok(conv, x):
     return supported and tiles >= (1 if invariant() else CONV_HIP_MIN_TILES)
 
 
+CONV_PAIR = os.environ.get("DS_CONV_PAIR", "1") != "0"          # A/B switch: two small 3x3 convolutions in one launch = ds_conv3x3_nhwc_pair
+
+
+def conv2d_pair(conv0, x0, conv1, x1):
+    """(conv0(x0), conv1(x1)).  Two launches that each fill only part of one round of the persistent kernel, and together still at
+    most one round, cost one tile's K loop EACH; walked as one tile list (ds_conv3x3_nhwc_pair) they cost it once.  Taken when both
+    convolutions go in-tree anyway, are bias-free with common channels, and their tiles together fit one workgroup per CU; the same
+    bits as two conv2d calls."""
+    if CONV_PAIR and conv3x3_hip_ok(conv0, x0) and conv3x3_hip_ok(conv1, x1):
+        from . import _native
+        if _native.conv3x3_pair_supported(conv0, x0, conv1, x1):
+            tiles = sum((x.shape[0] * x.shape[2] * x.shape[3] + 255) // 256 for x in (x0, x1)) * (conv0.out_channels // 256)
+            if tiles <= torch.cuda.get_device_properties(x0.device).multi_processor_count // 8 * 8:
+                return _native.conv3x3_pair(conv0, x0, conv1, x1)
+    return conv2d(conv0, x0), conv2d(conv1, x1)
+
+
 def conv2d(conv, x):
     """conv(x): ds_conv3x3_nhwc[_circular] where it applies (scratch.layerN_rn of the decoders), the library otherwise."""
     if conv3x3_hip_ok(conv, x):
@@ -570,6 +587,7 @@ CONV_BIAS_HIP = os.environ.get("DS_CONV_BIAS", "1") != "0"          # A/B switch
 CONV1X1_HIP = os.environ.get("DS_CONV1X1", "1") != "0"            # 1x1 convolutions (reassemble, fusion blocks' out_conv) = ds_linear on NHWC rows
 CONVT_HIP = os.environ.get("DS_CONVT", "1") != "0"                # ConvTranspose2d with kernel == stride = ds_linear_shuffle
 READOUT_HIP = os.environ.get("DS_READOUT", "1") != "0"            # the read-out projection on the padded taps = ds_linear_readout
+READOUT_CLS4 = os.environ.get("DS_READOUT_CLS4", "1") != "0"      # A/B switch: the four read-outs' cls vectors in one launch = ds_linear_rows4
 CONV1X1_MIN_TILES = int(os.environ.get("DS_CONV1X1_MIN_TILES", 96))
 
 
