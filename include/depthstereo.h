@@ -112,6 +112,7 @@ int ds_profile_last_ms(ds_ctx *ctx, float *render_ms, float *exact_ms);
 #define DS_KT_LINEAR_READOUT   6   /* ds_linear_readout */
 #define DS_KT_LINEAR_SHUFFLE   7   /* ds_linear_shuffle */
 #define DS_KT_NORMALMAP        8   /* ds_normalmap (uint16, the fused kernel) */
+#define DS_KT_DEPTH_REFINE     9   /* ds_joint_bilateral_u16 */
 #define DS_KT_RAGGED          12   /* + kind: the ragged round (k_linear_ragged) of that GEMM kind */
 int ds_kernel_timer_enable(ds_ctx *ctx, int enable);
 int ds_kernel_timer_read(ds_ctx *ctx, int kind, int64_t *launches, double *total_ms);
@@ -237,6 +238,35 @@ int ds_normalmap_gradient_blur_f32_wrap(ds_ctx *ctx, const float *depth, int n, 
  */
 int ds_bilateral_u16(ds_ctx *ctx, const uint16_t *depth, int n, int h, int w, int radius, const double *ws, const double *wr,
                      int wrap, double *out, void *stream);
+
+/*
+ * ds_joint_bilateral_u16 -- depth refinement: the joint (cross) bilateral filter of a uint16 depth map guided by the image.  The
+ * spatial kernel is a Gaussian; the range weight is taken from the COLOUR difference of the guide, not from the depth, so depth
+ * averages only within a colour region and a silhouette's ramp collects at the colour edge.  The reference has no counterpart; this
+ * comment is the definition.
+ * depth D [n,h,w] uint16, guide G [n,h,w,c] uint8 dense with c = guide_channels in {3, 4} -> out [n,h,w] uint16.  Only the first three
+ * bytes of a guide pixel are read; for c == 4 the fourth byte is ignored.
+ *   ws: (2 radius + 1)^2 float64 spatial weights in raster order (dy outer, dx inner, both -radius..radius), made on the host exactly
+ *       as for ds_bilateral_u16: exp(-(dx^2 + dy^2) / (2 sigma_space^2)) where dx^2 + dy^2 <= radius^2, exactly 0.0 outside that circle;
+ *   wc: 766 float64 colour weights, wc[k] = exp(-k^2 / (2 sigma_color^2)), made on the host.  Its argument is the INTEGER
+ *       k(q, p) = |R_q - R_p| + |G_q - G_p| + |B_q - B_p|, in 0..765: no exp runs on the device, and sigma_color is in units of summed
+ *       8-bit channel difference.
+ *   For pixel p: num = den = 0; for every tap t in raster order with ws[t] != 0: q = p + (dy, dx) after the border rule;
+ *       wgt = ws[t] * wc[k(q, p)];  num = num + wgt * (double)D(q) (the product rounded, then the sum: no fused multiply-add);
+ *       den = den + wgt.  Then F = num / den, one IEEE division, and out(p) = (uint16) rint(F), round-half-to-even.
+ *   The centre tap makes den >= 1.  F is a convex combination of uint16 values, so rint(F) lies in 0..65535: no clamp is part of the
+ *   definition.
+ *   Borders: wrap == 0 BORDER_REFLECT_101 (radius < min(h, w) required), wrap != 0 tap index modulo the image size (any size); the same
+ *   rule for D and G.
+ * One accumulation chain per pixel: a pixel's bits depend neither on the tiling of the launch, nor on the batch size, nor on its
+ * position in the batch; a float64 NumPy loop over the taps gives the same bits (tests/depth_refine_cases.py).  Iterations are a host
+ * loop over this entry point between two buffers: pass i + 1 filters the uint16 result of pass i with the same guide.
+ * DS_EINVAL: a null pointer; n, h or w <= 0; guide_channels not in {3, 4}; radius outside 1..15; radius >= min(h, w) without wrap; out
+ * overlapping depth; ws or wc not 8-byte aligned, depth or out not 2-byte aligned (the guide may have any alignment).
+ * DS_EUNSUPPORTED: n > 65535 or h > 32 * 65535.  Asynchronous on `stream`; the kernel timer DS_KT_DEPTH_REFINE brackets the launch.
+ */
+int ds_joint_bilateral_u16(ds_ctx *ctx, const uint16_t *depth, const uint8_t *guide, int guide_channels, int n, int h, int w, int radius,
+                           const double *ws, const double *wc, int wrap, uint16_t *out, void *stream);
 
 /*
  * ds_frame_luma_hist -- per-frame luma histograms of a uint8 clip: the input of video mode's scene-cut detector (the reference

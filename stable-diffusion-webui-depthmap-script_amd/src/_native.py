@@ -27,7 +27,7 @@ EXPORTS = [
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
-    "ds_bilateral_u16", "ds_frame_luma_hist", "ds_temporal_smooth5_f32",
+    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_frame_luma_hist", "ds_temporal_smooth5_f32",
     "ds_preprocess_bicubic_rows", "ds_tokens_fixup", "ds_upsample_bicubic_to_f32", "ds_im2col3x3_s2_nhwc",
 ]
 
@@ -85,6 +85,7 @@ def lib():
             for name in ("ds_normalmap", "ds_normalmap_f64", "ds_normalmap_gradient_f32", "ds_normalmap_gradient_f16", "ds_normalmap_gradient_blur_f32"):
                 getattr(L, name + "_wrap").argtypes = getattr(L, name).argtypes
             L.ds_bilateral_u16.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, ci, vp, vp]
+            L.ds_joint_bilateral_u16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp]
             L.ds_frame_luma_hist.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_smooth5_f32.argtypes = [vp, vp, ci, i64, ci, ci, ci, ci, vp, vp]
             L.ds_depth_to_u16.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp]
@@ -376,6 +377,96 @@ def bilateral_u16(depth_u16, d, sigma_color, sigma_space, wrap=False):
     _check(lib().ds_bilateral_u16(ctx_for(_dev_index(depth_u16)), depth_u16.data_ptr(), n, h, w, d // 2, tabs[0].data_ptr(),
                                   tabs[1].data_ptr(), 1 if wrap else 0, out.data_ptr(), _stream(depth_u16)))
     return out
+
+
+# ---- depth refinement (csrc/ds_joint_bilateral.hip; public interface: src/depth_refine.py) ------------------------------------------
+_DEPTH_REFINE_TABLES = collections.OrderedDict()       # (device index, d, sigma_color, sigma_space) -> (ws, wc) on that device
+_DEPTH_REFINE_TABLES_MAX = 4
+_DEPTH_REFINE_LOCK = threading.Lock()
+DEPTH_REFINE_MAX_ITERATIONS = 8
+
+
+def depth_refine_params(p):
+    """(d, sigma_color, sigma_space) or (d, sigma_color, sigma_space, iterations) as (int, float, float, int), or ValueError: d odd in
+    3..31, both sigmas finite and > 0, iterations an integer in 1..8 (default 1); a bool is no integer.  Pure Python (the funnel
+    checks its option with it before any device work)."""
+    try:
+        if isinstance(p, (str, bytes)) or len(p) not in (3, 4):
+            raise TypeError
+        d, sigma_color, sigma_space = p[0], p[1], p[2]
+        it = p[3] if len(p) == 4 else 1
+        ok_d = not isinstance(d, bool) and int(d) == d
+        ok_it = not isinstance(it, bool) and int(it) == it
+        d, sigma_color, sigma_space, it = int(d), float(sigma_color), float(sigma_space), int(it)
+    except (TypeError, ValueError, OverflowError, KeyError, IndexError):
+        raise ValueError("depth_refine must be (d, sigma_color, sigma_space) or (d, sigma_color, sigma_space, iterations), got %r" % (p,)) from None
+    if not (ok_d and d % 2 == 1 and 3 <= d <= 31):
+        raise ValueError("depth_refine: d must be an odd integer in 3..31, got %r" % (p[0],))
+    if not (0.0 < sigma_color < math.inf and 0.0 < sigma_space < math.inf):
+        raise ValueError("depth_refine: sigma_color and sigma_space must be finite and > 0, got %r, %r" % (sigma_color, sigma_space))
+    if not (ok_it and 1 <= it <= DEPTH_REFINE_MAX_ITERATIONS):
+        raise ValueError("depth_refine: iterations must be an integer in 1..%d, got %r" % (DEPTH_REFINE_MAX_ITERATIONS, p[3] if len(p) == 4 else it))
+    return d, sigma_color, sigma_space, it
+
+
+def depth_refine_tables(d, sigma_color, sigma_space):
+    """The two host-made tables of ds_joint_bilateral_u16 (include/depthstereo.h), float64: ws (d * d, raster order, exactly 0 outside
+    the circle of radius d // 2) and wc (766, indexed by the integer |dR| + |dG| + |dB| of two guide pixels)."""
+    r = d // 2
+    dy, dx = np.mgrid[-r:r + 1, -r:r + 1]
+    ws = np.where(dx * dx + dy * dy <= r * r, np.exp(-(dx * dx + dy * dy) / (2.0 * sigma_space**2)), 0.0).astype(np.float64).ravel()
+    wc = np.exp(-(np.arange(766, dtype=np.float64)**2) / (2.0 * sigma_color**2))
+    return ws, wc
+
+
+def joint_bilateral_u16(depth_u16, guide_u8, d, sigma_color, sigma_space, iterations=1, wrap=False):
+    """Joint bilateral filter of uint16 depth maps [n,h,w] (cuda) guided by uint8 images [n,h,w,c], c in {3, 4} (cuda, same device,
+    any byte alignment; only the first three channels are read) -> uint16 [n,h,w] (ds_joint_bilateral_u16: the definition is in
+    include/depthstereo.h).  d: odd window diameter 3..31; sigma_color in units of summed 8-bit channel difference; sigma_space in
+    pixels; iterations 1..8: pass i + 1 filters the result of pass i with the same guide (one launch each, between two buffers);
+    wrap: tap indices modulo the image size instead of BORDER_REFLECT_101 (which needs d // 2 < min(h, w)).  The tables are made on
+    the host, uploaded once and kept for the last 4 (device, d, sigma_color, sigma_space)."""
+    torch = require_gpu()
+    try:
+        d, sigma_color, sigma_space, iterations = depth_refine_params((d, sigma_color, sigma_space, iterations))
+    except ValueError as e:
+        raise DepthStereoError("joint_bilateral_u16: %s" % e) from None
+    if not (torch.is_tensor(depth_u16) and depth_u16.is_cuda and depth_u16.dtype == torch.uint16 and depth_u16.dim() == 3):
+        raise DepthStereoError("joint_bilateral_u16: depth must be a uint16 cuda tensor [n,h,w], got %s %s"
+                               % (getattr(depth_u16, "dtype", type(depth_u16)), tuple(getattr(depth_u16, "shape", ()))))
+    if not (torch.is_tensor(guide_u8) and guide_u8.is_cuda and guide_u8.dtype == torch.uint8 and guide_u8.dim() == 4
+            and guide_u8.device == depth_u16.device and tuple(guide_u8.shape[:3]) == tuple(depth_u16.shape) and guide_u8.shape[3] in (3, 4)):
+        raise DepthStereoError("joint_bilateral_u16: guide must be a uint8 cuda tensor [n,h,w,3 or 4] on the depth's device and of its "
+                               "size %s, got %s %s" % (tuple(depth_u16.shape), getattr(guide_u8, "dtype", type(guide_u8)),
+                                                       tuple(getattr(guide_u8, "shape", ()))))
+    depth_u16, guide_u8 = depth_u16.contiguous(), guide_u8.contiguous()
+    n, h, w = depth_u16.shape
+    if n == 0 or h == 0 or w == 0:
+        raise DepthStereoError("joint_bilateral_u16: empty depth %s" % (tuple(depth_u16.shape),))
+    if not wrap and d // 2 >= min(h, w):
+        raise DepthStereoError("joint_bilateral_u16: d // 2 = %d must be below min(h, w) = %d without wrap" % (d // 2, min(h, w)))
+    key = (_dev_index(depth_u16), d, sigma_color, sigma_space)
+    with _DEPTH_REFINE_LOCK:
+        tabs = _DEPTH_REFINE_TABLES.get(key)
+        if tabs is None:
+            ws, wc = depth_refine_tables(d, sigma_color, sigma_space)
+            tabs = _DEPTH_REFINE_TABLES[key] = (torch.from_numpy(ws).to(depth_u16.device), torch.from_numpy(wc).to(depth_u16.device))
+            while len(_DEPTH_REFINE_TABLES) > _DEPTH_REFINE_TABLES_MAX:
+                _DEPTH_REFINE_TABLES.popitem(last=False)
+        else:
+            _DEPTH_REFINE_TABLES.move_to_end(key)
+    for t in tabs:                   # an evicted table may still be read by a launch on this stream: tell the allocator
+        t.record_stream(torch.cuda.current_stream(depth_u16.device))
+    src = depth_u16
+    bufs = [torch.empty((n, h, w), dtype=torch.uint16, device=depth_u16.device) for _ in range(min(iterations, 2))]
+    for i in range(iterations):
+        out = bufs[i & 1]
+        CALLS["ds_joint_bilateral_u16"] += 1
+        _check(lib().ds_joint_bilateral_u16(ctx_for(_dev_index(depth_u16)), src.data_ptr(), guide_u8.data_ptr(), guide_u8.shape[3], n, h, w,
+                                            d // 2, tabs[0].data_ptr(), tabs[1].data_ptr(), 1 if wrap else 0, out.data_ptr(),
+                                            _stream(depth_u16)))
+        src = out
+    return src
 
 
 # ---- video mode (csrc/ds_video.hip; host half: src/video_mode.py) ------------------------------------------------------------------
@@ -941,7 +1032,7 @@ def dwconv(x, w_taps, bias_in, bias, kernel, stride, pad_top, pad_left, out_hw):
 
 
 KT_KINDS = {"linear_gelu": 0, "attention": 1, "linear_residual": 2, "linear": 3, "linear_vt": 4, "conv3x3": 5, "linear_readout": 6,
-            "linear_shuffle": 7, "normalmap": 8}
+            "linear_shuffle": 7, "normalmap": 8, "depth_refine": 9}
 KT_RAGGED = 12
 
 

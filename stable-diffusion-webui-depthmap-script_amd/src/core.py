@@ -438,7 +438,8 @@ def _mark(g, name, stream=None):
     g.setdefault("trace", []).append((name, ev, _time.perf_counter()))
 
 
-def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=None, normalmap_wrap=False, normalmap_bilateral=None):
+def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=None, normalmap_wrap=False, normalmap_bilateral=None,
+                  depth_refine=None, depth_refine_wrap=False):
     """Enqueue everything a group needs on the current stream -- H2D, network, post-processing, stereo, normal map, heat
     map, D2H into pinned buffers -- and return the handles; nothing here waits for the device except the post-processing
     branches that must know which predictions are flat (one sync per batch) and the percentile bisection of 'Outliers'."""
@@ -519,7 +520,7 @@ def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=Non
         # (RGB images that own their pixel store go through Pillow's Arrow export + memmove: _rgbx_pixels above; everything
         # else takes np.asarray)
         img_t = upload_pixels("img", lambda im: np.asarray(im, dtype=np.uint8), rgb=images[0].mode == "RGB")
-    mesh_source = None
+    mesh_source = rgb_t = None
     if custom:
         out_t = _ingest_custom_depth([inputdepthmaps[i] for i in idxs], (w, h), device, upload, stats)   # :145-174
         d16 = _native.convert_to_i16(out_t)                                                      # :211
@@ -569,6 +570,18 @@ def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=Non
             if any(broken):                                                                      # :203-206 zeros
                 keep = torch.tensor([0 if x else 1 for x in broken], device=device, dtype=torch.int16).view(-1, 1, 1)
                 d16 = (d16.view(torch.int16) * keep).view(torch.uint16)
+    if depth_refine is not None:
+        # ops['depth_refine']: from here on d16 is its joint bilateral refinement guided by the image's RGB pixels (src/depth_refine.py)
+        # -- what the depth output, the stereo pair, the normal map and the heat map consume.  mesh_source and the raw prediction of
+        # DO_OUTPUT_DEPTH_PREDICTION stay what the network (or the caller) gave.  The guide: pixels already on the device where they are
+        if images[0].mode == "RGB" and img_t is not None:
+            guide_t = img_t
+        elif rgb_t is not None:
+            guide_t = rgb_t
+        else:
+            guide_t = upload_pixels("guide", lambda im: np.asarray(im.convert("RGB"), dtype=np.uint8), rgb=images[0].mode == "RGB")
+        from .depth_refine import refine_depthmap_batch
+        d16 = refine_depthmap_batch(d16, guide_t, depth_refine, depth_refine_wrap)
     g["d16"], g["mesh_source"], g["img_t"], g["custom"] = d16, mesh_source, img_t, custom
 
     # results go back on a COPY STREAM of their own: the device-to-host copies of this group (11 MB per 1024^2 unit) then run
@@ -895,7 +908,21 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
     normalmap_bilateral = ops.get('normalmap_bilateral')
     if normalmap_bilateral is not None:
         normalmap_bilateral = _native.bilateral_params(normalmap_bilateral)
-    model_holder.update_settings(**{k: v for k, v in ops.items() if k not in ('normalmap_wrap', 'normalmap_bilateral')})
+    # ops['depth_refine'] (not in the reference): (d, sigma_color, sigma_space[, iterations]) = the joint bilateral refinement of the
+    # uint16 depth map guided by the input image (src/depth_refine.py), applied before every consumer of that map; absent / None = off,
+    # and then the call makes the launches, uploads and bytes it always made.  ops['depth_refine_wrap']: True, False or 'tiling' (exactly
+    # when TILING_MODE is on), the filter's border rule.  Options of THIS call, checked here before any device work.
+    depth_refine = ops.get('depth_refine')
+    if depth_refine is not None:
+        depth_refine = _native.depth_refine_params(depth_refine)
+    depth_refine_wrap = ops.get('depth_refine_wrap', False)
+    if isinstance(depth_refine_wrap, str):
+        if depth_refine_wrap != 'tiling':
+            raise ValueError("ops['depth_refine_wrap'] must be True, False or 'tiling', got %r" % (depth_refine_wrap,))
+        depth_refine_wrap = bool(inp[go.TILING_MODE])
+    depth_refine_wrap = bool(depth_refine_wrap)
+    model_holder.update_settings(**{k: v for k, v in ops.items()
+                                    if k not in ('normalmap_wrap', 'normalmap_bilateral', 'depth_refine', 'depth_refine_wrap')})
 
     torch = _native.require_gpu()        # the hot path has no CPU implementation, whatever COMPUTE_DEVICE says
     device = torch.device('cuda', torch.cuda.current_device())
@@ -926,7 +953,7 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
             try:
                 _t0 = _time.perf_counter()
                 launched, failure = _launch_group(gi & 1, idxs, inputimages, inputdepthmaps, inp, device, stats, normalmap_wrap,
-                                                  normalmap_bilateral), None
+                                                  normalmap_bilateral, depth_refine, depth_refine_wrap), None
                 stats["launch"] = stats.get("launch", 0.0) + (_time.perf_counter() - _t0)
             except Exception as e:          # noqa: BLE001 -- re-raised below, after the results that precede it
                 launched, failure = None, e
