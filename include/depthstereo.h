@@ -466,7 +466,9 @@ int ds_reassemble_readout(ds_ctx *ctx, const void *proj, const void *clsvec, voi
  *     out = [relu]( x + bias[channel] [+ res1] [+ res2] )
  * (ResidualConvUnit_custom, dmidas/blocks.py:352-377; ResidualConvUnit, ddepth_anything_v2/.../util/blocks.py:56-85; the
  * skip add of the fusion blocks).  x, res1, res2, out: `elements` values, channel fastest; res1 / res2 may be NULL; out may
- * alias x.  f16/bf16, channels % 8 == 0.
+ * alias x.  f16/bf16, channels % 8 == 0.  The sum is taken in float32 (x + bias, + res1, + res2, in that order) and rounded once.
+ * NaN rule (this entry point and ds_dwconv_nhwc): an activation function never hides a NaN.  relu(NaN) = NaN and relu6(NaN) = NaN,
+ * as torch's ReLU and ReLU6 (hardtanh) give; relu(-0.0) may be either zero.
  */
 int ds_bias_act_nhwc(ds_ctx *ctx, const void *x, const void *bias, const void *res1, const void *res2, void *out,
                      int64_t elements, int channels, int relu, int dtype, void *stream);
@@ -756,6 +758,8 @@ int ds_bias_act_f32(ds_ctx *ctx, const float *x, const float *bias, const float 
  * the bottom / right padding follows from out_h / out_w and lies in (-stride, kernel).  channels % 8 == 0, operands 16-byte aligned,
  * y must not alias x (DS_EINVAL otherwise; bf16: DS_EUNSUPPORTED).  fp32 accumulation in ky-major tap order, + bias, one rounding to
  * the output type: an image's output does not depend on the batch size or on its position in the batch.  No workspace.
+ * min / max above follow the NaN rule stated at ds_bias_act_nhwc: a NaN in x (or in a sum) stays NaN, so it reaches exactly the
+ * outputs of its channel whose window holds it.
  */
 int ds_dwconv_nhwc(ds_ctx *ctx, const void *x, const float *w, const float *bias_in, const float *bias, void *y, int batch, int in_h,
                    int in_w, int channels, int out_h, int out_w, int kernel, int stride, int pad_top, int pad_left, int dtype, void *stream);

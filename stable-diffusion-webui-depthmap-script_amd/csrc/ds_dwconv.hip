@@ -21,7 +21,8 @@
 
 typedef float dw_f4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float dw_relu6(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
+// ReLU6 as torch's hardtanh computes it: a NaN stays NaN (fminf(fmaxf(v, 0), 6) would turn it into 0)
+__device__ __forceinline__ float dw_relu6(float v) { return v < 0.f ? 0.f : (v > 6.f ? 6.f : v); }
 
 template <typename T> struct dw_io;
 template <> struct dw_io<_Float16> {

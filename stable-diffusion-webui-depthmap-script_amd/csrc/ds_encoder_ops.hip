@@ -1080,7 +1080,7 @@ __global__ __launch_bounds__(256) void k_bias_act_nhwc(const void *x_, const voi
             float f = (float)xv[t] + (float)bv[t];
             if (r1) f += (float)av[t];
             if (r2) f += (float)cv[t];
-            if (relu) f = f > 0.f ? f : 0.f;
+            if (relu) f = f < 0.f ? 0.f : f;              // a NaN stays NaN, like torch's ReLU and gc_relu
             ov[t] = (T)f;
         }
         __builtin_memcpy(out + (size_t)i * 8, ov, 16);

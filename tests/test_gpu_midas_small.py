@@ -117,6 +117,29 @@ def test_dwconv_batch_invariance(gpu, dtype):
         assert torch.equal(y3[2:3], y1), (k, s, c, h, w)
 
 
+@pytest.mark.parametrize("dtype", [torch.float16, torch.float32])
+@pytest.mark.parametrize("k", [3, 5])
+def test_dwconv_nan_reaches_exactly_the_windows_that_hold_it(gpu, dtype, k):
+    """One NaN input element gives NaN at exactly the outputs of its channel whose window holds it -- ReLU6 propagates NaN like the
+    reference's nn.ReLU6 (hardtanh) and like the clamp of _definition; every other output keeps the bits of the run without it."""
+    from src import _native
+    g = torch.Generator().manual_seed(9)
+    for s, (b, c, h, w), (n, ch, iy, ix) in [(1, (2, 32, 9, 12), (1, 5, 4, 6)), (2, (3, 144, 11, 10), (2, 143, 0, 9)), (1, (1, 192, 8, 8), (0, 64, 7, 0))]:
+        pt, pl, oh, ow = _pads(k, s, "same", h, w)
+        x, wt, bi, bo = _operands(g, b, c, h, w, k, dtype)
+        clean = _native.dwconv(x, wt, bi, bo, k, s, pt, pl, (oh, ow))
+        x[n, ch, iy, ix] = float("nan")
+        y = _native.dwconv(x, wt, bi, bo, k, s, pt, pl, (oh, ow)).cpu()
+        oy, ox = torch.arange(oh).view(-1, 1), torch.arange(ow).view(1, -1)
+        hit = (oy * s - pt <= iy) & (iy < oy * s - pt + k) & (ox * s - pl <= ix) & (ix < ox * s - pl + k)
+        want = torch.zeros((b, c, oh, ow), dtype=torch.bool)
+        want[n, ch] = hit
+        case = (k, s, (b, c, h, w), (n, ch, iy, ix))
+        assert bool(hit.any()) and torch.equal(torch.isnan(y), want), (case, int(torch.isnan(y).sum()), int(want.sum()))
+        assert torch.equal(torch.isnan(_definition(x, wt, bi, bo, k, s, pt, pl, oh, ow)), want), case
+        assert torch.equal(y[~want], clean.cpu()[~want]), case
+
+
 def test_dwconv_argument_checks(gpu):
     from src import _native
     L = _native.lib()

@@ -59,8 +59,8 @@ def smooth_depth(H, W, seed):
 
 
 # ---- exact-integer operands and per-element rounding bounds for the half-precision GEMM / convolution tests ------------------------
-MANTISSA_BITS = {"float16": 10, "bfloat16": 7}
-MIN_NORMAL_EXP = {"float16": -14, "bfloat16": -126}
+MANTISSA_BITS = {"float16": 10, "bfloat16": 7, "float32": 23}
+MIN_NORMAL_EXP = {"float16": -14, "bfloat16": -126, "float32": -126}
 
 
 def ternary(g, shape, density):
@@ -78,7 +78,7 @@ def small_ints(g, shape, bound):
 
 
 def ulp_spacing(ref64, dtype):
-    """Spacing of `dtype` (float16 / bfloat16) at the float64 values rounded to it: 2^(floor(log2 |r|) - mantissa bits), and the
+    """Spacing of `dtype` (float16 / bfloat16 / float32) at the float64 values rounded to it: 2^(floor(log2 |r|) - mantissa bits), and the
     subnormal spacing below the smallest normal number (the construction of test_gpu_midas_small._f16_within_bound, for both types)."""
     import torch
     name = str(dtype).replace("torch.", "")
@@ -146,6 +146,67 @@ def bilinear_ref(x, size, align_corners=True, taps_x=None):
             v = x[:, torch.from_numpy(iy)[:, None], torch.from_numpy(ix)[None, :]]          # [B, oh, ow, C]
             u, s = u + w64 * v, s + w64 * v.abs()
     return u, s
+
+
+def bicubic_taps(n_in, n_out):
+    """One axis of the bicubic resize as include/depthstereo.h (ds_preprocess_bicubic) and pre_cubic (csrc/ds_common.h) define it, in
+    float32 like the kernels (the coordinate and weight arithmetic is part of the definition, every multiply and add rounded on its
+    own): s = n_in / n_out, f = s * (o + 0.5) - 0.5, t = f - floor(f), the four weights of the cubic convolution kernel with
+    A = -0.75 in pre_cubic's order of operations, indices clamp(floor(f) - 1 + k, 0, n_in - 1).  Returns (int64 [n_out, 4],
+    float32 [n_out, 4])."""
+    f32 = np.float32
+    o = np.arange(n_out, dtype=np.float32)
+    s = f32(n_in) / f32(n_out)
+    f = s * (o + f32(0.5)) - f32(0.5)
+    f0 = np.floor(f)
+    t = f - f0
+    a = f32(-0.75)
+    x0, x3, x2 = t + f32(1.0), f32(2.0) - t, f32(1.0) - t
+    c = np.stack([((a * x0 - f32(5.0) * a) * x0 + f32(8.0) * a) * x0 - f32(4.0) * a,
+                  ((a + f32(2.0)) * t - (a + f32(3.0))) * t * t + f32(1.0),
+                  ((a + f32(2.0)) * x2 - (a + f32(3.0))) * x2 * x2 + f32(1.0),
+                  ((a * x3 - f32(5.0) * a) * x3 + f32(8.0) * a) * x3 - f32(4.0) * a], axis=1)
+    assert f.dtype == np.float32 and c.dtype == np.float32
+    idx = np.clip(f0.astype(np.int64)[:, None] - 1 + np.arange(4, dtype=np.int64)[None, :], 0, n_in - 1)
+    return idx, c
+
+
+def triple(v):
+    """A scalar or three values -> float32 [3] (what the binding of ds_preprocess_bicubic passes to the library)."""
+    return np.asarray(tuple(v) if hasattr(v, "__len__") else (v,) * 3, dtype=np.float32)
+
+
+def preprocess_ref(img_u8, size, mean, std, flip):
+    """ds_preprocess_bicubic in float64: out[b, c] = (sum_ky sum_kx cy cx (px / 255) - mean_c) / std_c over the taps of bicubic_taps,
+    px the byte of image channel 2 - c (flip) or c; mean / std are the float32 values the binding passes, widened.  img_u8: uint8
+    [B, H, W, 3] (numpy or CPU tensor).  Returns (out, S) as float64 tensors [B, 3, oh, ow], S = sum |cy cx| px / 255."""
+    import torch
+    img = np.asarray(img_u8)
+    assert img.dtype == np.uint8 and img.ndim == 4 and img.shape[3] == 3
+    oh, ow = size
+    iy, cy = bicubic_taps(img.shape[1], oh)
+    ix, cx = bicubic_taps(img.shape[2], ow)
+    px = img.astype(np.float64) / 255.0
+    if flip:
+        px = px[..., ::-1]
+    acc = np.zeros((img.shape[0], oh, ow, 3))
+    s = np.zeros_like(acc)
+    for ky in range(4):
+        for kx in range(4):
+            w = cy[:, ky].astype(np.float64)[:, None] * cx[:, kx].astype(np.float64)[None, :]
+            v = px[:, iy[:, ky][:, None], ix[:, kx][None, :]]                       # [B, oh, ow, 3]
+            acc += w[None, :, :, None] * v
+            s += np.abs(w)[None, :, :, None] * v
+    out = (acc - triple(mean).astype(np.float64)) / triple(std).astype(np.float64)
+    return torch.from_numpy(np.ascontiguousarray(out.transpose(0, 3, 1, 2))), torch.from_numpy(np.ascontiguousarray(s.transpose(0, 3, 1, 2)))
+
+
+def gelu64(x):
+    """The exact GELU 0.5 x (1 + erf(x / sqrt 2)) of a float64 tensor, written with erfc (1 + erf(z) = erfc(-z)) so that the left
+    tail keeps its relative precision."""
+    import torch
+    x = x.double()
+    return 0.5 * x * torch.special.erfc(-x / 2.0 ** 0.5)
 
 
 def first_mismatches(got, want, limit=5):
