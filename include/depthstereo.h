@@ -301,6 +301,39 @@ int ds_temporal_smooth5_f32(ds_ctx *ctx, const float *src, int m, int64_t plane,
                             void *stream);
 
 /*
+ * ds_temporal_joint_bilateral_u16 -- video mode's temporal depth filter: the joint (cross) bilateral filter ALONG TIME of the uint16
+ * depth frames of a clip guided by its uint8 frames.  The depth at a pixel is averaged over the neighbouring frames of the same
+ * scene; the temporal kernel is a Gaussian, the range weight is taken from how much the PIXEL'S COLOUR changed between the two
+ * frames, so a static region loses the frame-to-frame noise of the network while a pixel that something moved over keeps its own
+ * depth (no ghosting).  The reference has no counterpart; this comment is the definition.
+ * depth D [m,h,w] uint16, guide G [m,h,w,c] uint8 dense with c = guide_channels in {3, 4} -> out [count,h,w] uint16.  Only the first
+ * three bytes of a guide pixel are read; for c == 4 the fourth byte is ignored.  The guide may have any byte alignment.
+ *   wt: radius + 1 float64 temporal weights made on the host, wt[a] = exp(-a^2 / (2 sigma_time^2)), wt[0] == 1.0;
+ *   wc: the 766 float64 colour weights of ds_joint_bilateral_u16, made by the same host code: wc[k] = exp(-k^2 / (2 sigma_color^2)).
+ *       No exp runs on the device; sigma_color is in units of summed 8-bit channel difference, sigma_time in frames.
+ *   For j < count, i = first + j and pixel p: num = den = 0.0; for u = -radius .. radius in increasing order, s = i + u:
+ *       a tap with s < lo or s > hi is OMITTED (not clamped: a weighted mean needs no replicated frame);
+ *       k = |R_s(p) - R_i(p)| + |G_s(p) - G_i(p)| + |B_s(p) - B_i(p)|, in 0..765;
+ *       wgt = wt[|u|] * wc[k];  num = num + wgt * (double)D_s(p) (the product rounded, then the sum: no fused multiply-add);
+ *       den = den + wgt.
+ *   Then F = num / den, one IEEE division, and out[j](p) = (uint16) rint(F), round-half-to-even.
+ *   The centre tap has weight exactly 1, so den >= 1.  F is a convex combination of uint16 values, so rint(F) lies in 0..65535: no
+ *   clamp is part of the definition.
+ * One accumulation chain per pixel and output frame: a pixel's bits depend only on the frames max(lo, i - radius) ..
+ * min(hi, i + radius) at that pixel -- not on first, not on count, not on how the launch tiles space or time, not on frames outside
+ * [lo, hi] (they are never read); a float64 NumPy loop over the taps gives the same bits (tests/video_stabilize_cases.py).  With lo
+ * and hi the first and last frame of a scene nothing is averaged across a cut.  A caller whose frames are sharded passes its halo
+ * plus its frames and first / lo / hi as indices into that, as for ds_temporal_smooth5_f32.
+ * DS_EINVAL: a null pointer; m, h, w or count <= 0; guide_channels not in {3, 4}; radius outside 1..4; 0 <= lo <= first,
+ * first + count - 1 <= hi or hi < m broken; wt or wc not 8-byte aligned; depth or out not 2-byte aligned; out overlapping depth
+ * (neighbouring frames are read: nothing is in place).  DS_EUNSUPPORTED: h * w >= 2^32.  Asynchronous on `stream`; one kernel, no
+ * workspace, no allocation.
+ */
+int ds_temporal_joint_bilateral_u16(ds_ctx *ctx, const uint16_t *depth, const uint8_t *guide, int guide_channels, int m, int h, int w,
+                                    int radius, const double *wt, const double *wc, int first, int count, int lo, int hi, uint16_t *out,
+                                    void *stream);
+
+/*
  * ds_normalmap_selfcheck -- device self-test of the fused normal-map kernels' arithmetic (tests): their square root and reciprocal
  * are the generic float64 expansions WITHOUT range scaling and special-case fix-ups (dead for n^2 = zx^2 + zy^2 + 1 in [1, 2^22],
  * src/normalmap_generation.py:34-39); the kernel compares them with sqrt() and 1.0 / n on n^2 = K / 2^18, K = k0 + stride * i,

@@ -1,5 +1,5 @@
-// Video mode's two kernels on gfx950 (include/depthstereo.h holds the definitions; the reference has neither: src/video_mode.py:114,
-// "TODO: Detect cuts and process segments separately").
+// Video mode's three kernels on gfx950 (include/depthstereo.h holds the definitions; the reference has none of them: src/video_mode.py:114,
+// "TODO: Detect cuts and process segments separately", and nothing that smooths the OUTPUT depth along time).
 //
 // ds_frame_luma_hist: a 256-bin histogram of the integer luma of every frame of a uint8 clip (what the cut detector compares between
 //   neighbouring frames).  Memory bound: every byte of the clip is read once, 1 KiB per frame is written.
@@ -27,6 +27,32 @@
 //   Rounding: every product and every sum is a separate binary32 operation.  This relies on contraction being OFF -- the pragma
 //   below and the library's -ffp-contract=off -- not on __fmul_rn / __fadd_rn, which are plain `*` and `+` to this compiler and
 //   would be contracted like them.  Subnormals are kept (the target's default float32 mode).
+//
+// ds_temporal_joint_bilateral_u16: the joint bilateral filter ALONG TIME of uint16 depth frames guided by the uint8 frames (the depth
+//   of a pixel averaged over the neighbouring frames of its scene, weighted by how little the pixel's colour changed).  The shape of
+//   the 5-tap filter above: a thread OWNS its pixels (TJ_PPT of them, TJ_THREADS apart) and walks the frames with a window of
+//   2 R + 1 packed guide words (R, G, B, 0) and as many depths in registers, shifted by one frame per output; R is a template
+//   parameter (1..4), every window index is a compile-time constant after unrolling, so the window is never an indexed array in
+//   scratch (the ISA of all four instantiations has no scratch).  Each depth value and each guide byte is loaded
+//   ONCE per launch (per time chunk, below); the frame that enters the window for the next output is requested before the current
+//   output is computed.  Taps outside [lo, hi] are OMITTED without a branch: the test is on the frame index alone, such a tap gets the
+//   weight +0.0, which leaves both sums as they are bit for bit, and its window slot is filled from the nearest frame inside [lo, hi]
+//   (at a scene's ends a frame is therefore requested again, from the cache; a frame outside the scene is never read -- it may lie
+//   outside the tensor).  With the loads unconditional the compiler waits for them where they are used, one output later, not where
+//   they are issued.
+//     * The guide is read byte by byte, three loads per pixel and frame: with c == 3 and an odd plane every frame sits at another
+//       byte alignment, and the base may be any address.  A wave's three loads cover the same 192 (256) contiguous bytes, so the
+//       second and third hit the lines the first brought in; k is then ONE v_sad_u8 of two packed words, as in ds_joint_bilateral.hip.
+//     * wc (766 float64) is indexed PER LANE by k.  It is staged in LDS (6 KiB) once per workgroup, as ds_joint_bilateral.hip does: a
+//       per-lane gather from memory would cost one address per lane in the vector memory path for every tap, next to the frame
+//       loads the kernel lives on; in LDS it is one ds_read_b64 whose lanes mostly ask for the same few small k on static content
+//       (broadcast) and spread over the 32 bank pairs on moving content.  wt (R + 1 values, the same for every lane) is read once
+//       into registers.
+//     * Arithmetic per tap: wt * wc, the product with the depth, two sums, all float64 and each rounded on its own (contraction is
+//       off, see above); one IEEE division and v_rndne_f64 per output.
+//     * Short clips of small frames: when the pixels alone give fewer than TJ_MIN_BLOCKS workgroups, the outputs are split into
+//       chunks of at least TJ_MIN_CHUNK frames over grid.y and every chunk primes its own window (2 R more frame reads per chunk).
+//       A pixel's chain of operations is the same in every chunking, so the bits do not depend on it.
 #include "ds_common.h"
 
 #pragma clang fp contract(off)
@@ -186,6 +212,142 @@ DS_API int ds_temporal_smooth5_f32(ds_ctx *ctx, const float *src, int m, int64_t
     const int64_t blocks = (plane + TS_THREADS * TS_PPT - 1) / (TS_THREADS * TS_PPT);
     DS_HIP_CHECK(hipSetDevice(ctx->device));
     hipLaunchKernelGGL(k_temporal_smooth5_f32, dim3((unsigned)blocks), dim3(TS_THREADS), 0, stream, src, plane, first, count, lo, hi, out);
+    DS_HIP_CHECK(hipGetLastError());
+    return DS_OK;
+}
+
+// ---- temporal joint bilateral filter ------------------------------------------------------------------------------------------------
+#define TJ_THREADS 256
+#define TJ_PPT 2
+#define TJ_WC 766                   // 3 * 255 + 1 colour differences
+#define TJ_MIN_BLOCKS 1024          // below this many workgroups from the pixels alone, the time axis is split over grid.y
+#define TJ_MIN_CHUNK 8              // ... into chunks of at least this many output frames
+
+__device__ __forceinline__ uint32_t tj_rgb(const uint8_t *px)      // three byte loads: any alignment, the fourth byte never read
+{
+    return (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16);
+}
+
+template <int R>
+__global__ __launch_bounds__(TJ_THREADS) void k_temporal_joint_bilateral_u16(const uint16_t *__restrict__ depth, const uint8_t *__restrict__ guide,
+                                                                             int gc, int64_t plane, int first, int count, int chunk, int lo,
+                                                                             int hi, const double *__restrict__ wt, const double *__restrict__ wc,
+                                                                             uint16_t *__restrict__ out)
+{
+    enum { W = 2 * R + 1 };
+    __shared__ double wc_lds[TJ_WC];
+    for (int i = threadIdx.x; i < TJ_WC; i += TJ_THREADS) wc_lds[i] = wc[i];
+    double t[R + 1];
+#pragma unroll
+    for (int a = 0; a <= R; a++) t[a] = wt[a];
+    __syncthreads();
+
+    const int j0 = (int)blockIdx.y * chunk;                              // this workgroup renders outputs j0 .. j1 - 1
+    const int j1 = j0 + chunk < count ? j0 + chunk : count;
+    const int64_t p0 = (int64_t)blockIdx.x * (TJ_THREADS * TJ_PPT) + threadIdx.x;
+    bool ok[TJ_PPT];
+    const uint16_t *dp[TJ_PPT];                                          // the pixel in frame 0; a frame is one uniform offset further
+    const uint8_t *gp[TJ_PPT];
+    uint16_t *op[TJ_PPT];
+    uint32_t g[TJ_PPT][W], d[TJ_PPT][W], gn[TJ_PPT], dn[TJ_PPT];
+#pragma unroll
+    for (int e = 0; e < TJ_PPT; e++) {
+        const int64_t p = p0 + (int64_t)e * TJ_THREADS;
+        ok[e] = p < plane;
+        dp[e] = depth + (ok[e] ? p : 0);                                 // a pixel past the plane reads pixel 0 and stores nothing
+        gp[e] = guide + (ok[e] ? p : 0) * gc;
+        op[e] = out + (ok[e] ? p : 0);
+    }
+    // The window of the first output.  A slot whose frame lies outside [lo, hi] gets the nearest frame inside instead (never an address
+    // outside the scene): its tap has weight +0.0 below, so what it holds does not matter, and no load hangs on a branch.
+#pragma unroll
+    for (int u = 0; u < W; u++) {
+        const int64_t fo = (int64_t)ts_clamp(first + j0 + u - R, lo, hi) * plane;
+#pragma unroll
+        for (int e = 0; e < TJ_PPT; e++) {
+            d[e][u] = dp[e][fo];
+            g[e][u] = tj_rgb(gp[e] + fo * gc);
+        }
+    }
+    for (int j = j0; j < j1; j++) {
+        const int i = first + j;
+        {                                                                // the last tap of the NEXT output, requested before this one is computed
+            const int64_t fo = (int64_t)ts_clamp(i + R + 1, lo, hi) * plane;
+#pragma unroll
+            for (int e = 0; e < TJ_PPT; e++) {
+                dn[e] = dp[e][fo];
+                gn[e] = tj_rgb(gp[e] + fo * gc);
+            }
+        }
+        double num[TJ_PPT], den[TJ_PPT];
+#pragma unroll
+        for (int e = 0; e < TJ_PPT; e++) num[e] = den[e] = 0.0;
+#pragma unroll
+        for (int u = 0; u < W; u++) {
+            const int s = i + u - R;
+            // A tap outside [lo, hi] is OMITTED.  Here: its weight is +0.0, and num + 0.0 * D == num, den + 0.0 == den bit for bit (every
+            // term is >= +0.0 and finite), so the chain has the bits it has without the tap -- and no branch splits the tap loop.
+            const double tw = (s >= lo && s <= hi) ? t[u < R ? R - u : u - R] : 0.0;
+#pragma unroll
+            for (int e = 0; e < TJ_PPT; e++) {
+                // |R_s - R_i| + |G_s - G_i| + |B_s - B_i| (+ |0 - 0|): one v_sad_u8; 0..765, inside the table by construction
+                const double wgt = tw * wc_lds[__builtin_amdgcn_sad_u8(g[e][u], g[e][R], 0u)];
+                const double prod = wgt * (double)d[e][u];
+                num[e] = num[e] + prod;
+                den[e] = den[e] + wgt;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < TJ_PPT; e++) {
+            if (ok[e]) op[e][(int64_t)j * plane] = (uint16_t)(unsigned)__builtin_rint(num[e] / den[e]);      // v_rndne_f64: half to even
+#pragma unroll
+            for (int u = 0; u + 1 < W; u++) {
+                d[e][u] = d[e][u + 1];
+                g[e][u] = g[e][u + 1];
+            }
+            d[e][W - 1] = dn[e];
+            g[e][W - 1] = gn[e];
+        }
+    }
+}
+
+DS_API int ds_temporal_joint_bilateral_u16(ds_ctx *ctx, const uint16_t *depth, const uint8_t *guide, int guide_channels, int m, int h, int w,
+                                           int radius, const double *wt, const double *wc, int first, int count, int lo, int hi,
+                                           uint16_t *out, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    DS_REQUIRE(ctx && depth && guide && wt && wc && out, DS_EINVAL, "ds_temporal_joint_bilateral_u16: null argument");
+    DS_REQUIRE(m > 0 && h > 0 && w > 0 && count > 0, DS_EINVAL, "ds_temporal_joint_bilateral_u16: bad size m=%d h=%d w=%d count=%d", m, h, w, count);
+    DS_REQUIRE(guide_channels == 3 || guide_channels == 4, DS_EINVAL, "ds_temporal_joint_bilateral_u16: guide_channels %d not 3 or 4", guide_channels);
+    DS_REQUIRE(radius >= 1 && radius <= 4, DS_EINVAL, "ds_temporal_joint_bilateral_u16: radius %d outside 1..4", radius);
+    DS_REQUIRE(0 <= lo && lo <= first && (int64_t)first + count - 1 <= hi && hi < m, DS_EINVAL,
+               "ds_temporal_joint_bilateral_u16: need 0 <= lo <= first, first + count - 1 <= hi < m (lo=%d first=%d count=%d hi=%d m=%d)",
+               lo, first, count, hi, m);
+    DS_REQUIRE((((uintptr_t)wt | (uintptr_t)wc) & 7) == 0 && (((uintptr_t)depth | (uintptr_t)out) & 1) == 0, DS_EINVAL,
+               "ds_temporal_joint_bilateral_u16: wt and wc must be 8-byte aligned, depth and out 2-byte aligned");
+    const uint64_t npix = (uint64_t)h * (uint64_t)w;
+    DS_REQUIRE(npix < (1ull << 32), DS_EUNSUPPORTED, "ds_temporal_joint_bilateral_u16: h * w = %llu must be below 2^32", (unsigned long long)npix);
+    const uintptr_t sb = (uintptr_t)depth, se = sb + (size_t)m * npix * sizeof(uint16_t);
+    const uintptr_t ob = (uintptr_t)out, oe = ob + (size_t)count * npix * sizeof(uint16_t);
+    DS_REQUIRE(oe <= sb || se <= ob, DS_EINVAL, "ds_temporal_joint_bilateral_u16: out overlaps depth");
+    const uint64_t blocks = (npix + TJ_THREADS * TJ_PPT - 1) / (TJ_THREADS * TJ_PPT);
+    int chunk = count;
+    if (blocks < TJ_MIN_BLOCKS) {
+        const uint64_t want = (TJ_MIN_BLOCKS + blocks - 1) / blocks;                 // chunks that would fill the device
+        chunk = (int)(((uint64_t)count + want - 1) / want);
+        if (chunk < TJ_MIN_CHUNK) chunk = TJ_MIN_CHUNK;
+        if (chunk > count) chunk = count;
+    }
+    const dim3 grid((unsigned)blocks, (unsigned)((count + chunk - 1) / chunk));      // grid.y <= TJ_MIN_BLOCKS
+    DS_HIP_CHECK(hipSetDevice(ctx->device));
+#define TJ_LAUNCH(R_)                                                                                                                  \
+    hipLaunchKernelGGL(k_temporal_joint_bilateral_u16<R_>, grid, dim3(TJ_THREADS), 0, stream, depth, guide, guide_channels, (int64_t)npix, \
+                       first, count, chunk, lo, hi, wt, wc, out)
+    if (radius == 1) TJ_LAUNCH(1);
+    else if (radius == 2) TJ_LAUNCH(2);
+    else if (radius == 3) TJ_LAUNCH(3);
+    else TJ_LAUNCH(4);
+#undef TJ_LAUNCH
     DS_HIP_CHECK(hipGetLastError());
     return DS_OK;
 }

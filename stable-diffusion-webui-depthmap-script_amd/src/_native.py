@@ -27,7 +27,7 @@ EXPORTS = [
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
-    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_frame_luma_hist", "ds_temporal_smooth5_f32",
+    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
     "ds_preprocess_bicubic_rows", "ds_tokens_fixup", "ds_upsample_bicubic_to_f32", "ds_im2col3x3_s2_nhwc",
 ]
 
@@ -88,6 +88,7 @@ def lib():
             L.ds_joint_bilateral_u16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp]
             L.ds_frame_luma_hist.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_smooth5_f32.argtypes = [vp, vp, ci, i64, ci, ci, ci, ci, vp, vp]
+            L.ds_temporal_joint_bilateral_u16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp]
             L.ds_depth_to_u16.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp]
             L.ds_convert_to_i16.argtypes = [vp, vp, ci, i64, vp, vp]
             L.ds_stereo_last_stats.argtypes = [vp, ctypes.POINTER(i64), vp]
@@ -409,14 +410,19 @@ def depth_refine_params(p):
     return d, sigma_color, sigma_space, it
 
 
+def color_weight_table(sigma_color):
+    """wc of ds_joint_bilateral_u16 and ds_temporal_joint_bilateral_u16: 766 float64, wc[k] = exp(-k^2 / (2 sigma_color^2)), indexed by
+    the integer |dR| + |dG| + |dB| of two guide pixels."""
+    return np.exp(-(np.arange(766, dtype=np.float64)**2) / (2.0 * sigma_color**2))
+
+
 def depth_refine_tables(d, sigma_color, sigma_space):
     """The two host-made tables of ds_joint_bilateral_u16 (include/depthstereo.h), float64: ws (d * d, raster order, exactly 0 outside
     the circle of radius d // 2) and wc (766, indexed by the integer |dR| + |dG| + |dB| of two guide pixels)."""
     r = d // 2
     dy, dx = np.mgrid[-r:r + 1, -r:r + 1]
     ws = np.where(dx * dx + dy * dy <= r * r, np.exp(-(dx * dx + dy * dy) / (2.0 * sigma_space**2)), 0.0).astype(np.float64).ravel()
-    wc = np.exp(-(np.arange(766, dtype=np.float64)**2) / (2.0 * sigma_color**2))
-    return ws, wc
+    return ws, color_weight_table(sigma_color)
 
 
 def joint_bilateral_u16(depth_u16, guide_u8, d, sigma_color, sigma_space, iterations=1, wrap=False):
@@ -510,6 +516,96 @@ def temporal_smooth5(src, first, count, lo, hi, out=None):
     CALLS["ds_temporal_smooth5_f32"] += 1
     _check(lib().ds_temporal_smooth5_f32(ctx_for(_dev_index(src)), src.data_ptr(), m, plane, int(first), int(count), int(lo), int(hi),
                                          out.data_ptr(), _stream(src)))
+    return out
+
+
+# the temporal depth filter (ds_temporal_joint_bilateral_u16; public interface: video_mode.stabilize_depth)
+_STABILIZE_TABLES = collections.OrderedDict()          # (device index, radius, sigma_color, sigma_time) -> (wt, wc) on that device
+_STABILIZE_TABLES_MAX = 4
+_STABILIZE_LOCK = threading.Lock()
+STABILIZE_MAX_RADIUS = 4
+
+
+def stabilize_params(params):
+    """(radius, sigma_color, sigma_time) as (int, float, float), or ValueError: radius an integer in 1..4 (a bool is no integer), both
+    sigmas finite and > 0.  Pure Python (gen_frames_sharded checks its option with it before any device work)."""
+    try:
+        if isinstance(params, (str, bytes)) or len(params) != 3:
+            raise TypeError
+        radius, sigma_color, sigma_time = params[0], params[1], params[2]
+        ok_r = not isinstance(radius, (bool, np.bool_)) and int(radius) == radius
+        radius, sigma_color, sigma_time = int(radius), float(sigma_color), float(sigma_time)
+    except (TypeError, ValueError, OverflowError, KeyError, IndexError):
+        raise ValueError("stabilize must be (radius, sigma_color, sigma_time), got %r" % (params,)) from None
+    if not (ok_r and 1 <= radius <= STABILIZE_MAX_RADIUS):
+        raise ValueError("stabilize: radius must be an integer in 1..%d, got %r" % (STABILIZE_MAX_RADIUS, params[0]))
+    if not (0.0 < sigma_color < math.inf and 0.0 < sigma_time < math.inf):
+        raise ValueError("stabilize: sigma_color and sigma_time must be finite and > 0, got %r, %r" % (sigma_color, sigma_time))
+    return radius, sigma_color, sigma_time
+
+
+def temporal_joint_bilateral_tables(radius, sigma_color, sigma_time):
+    """The two host-made tables of ds_temporal_joint_bilateral_u16 (include/depthstereo.h), float64: wt (radius + 1,
+    wt[a] = exp(-a^2 / (2 sigma_time^2)), wt[0] == 1.0) and wc (766: depth refinement's table, from the same code)."""
+    wt = np.exp(-(np.arange(radius + 1, dtype=np.float64)**2) / (2.0 * sigma_time**2))
+    return wt, color_weight_table(sigma_color)
+
+
+def stabilize_tables_on(device, radius, sigma_color, sigma_time):
+    """(wt, wc) of temporal_joint_bilateral_tables as float64 tensors on `device`; on a GPU they are uploaded once and kept for the
+    last 4 (device, radius, sigma_color, sigma_time)."""
+    torch = _torch()
+    device = torch.device(device)
+    if device.type != "cuda":
+        return tuple(torch.from_numpy(t) for t in temporal_joint_bilateral_tables(radius, sigma_color, sigma_time))
+    key = (device.index if device.index is not None else torch.cuda.current_device(), radius, sigma_color, sigma_time)
+    with _STABILIZE_LOCK:
+        tabs = _STABILIZE_TABLES.get(key)
+        if tabs is None:
+            tabs = _STABILIZE_TABLES[key] = tuple(torch.from_numpy(t).to(device)
+                                                  for t in temporal_joint_bilateral_tables(radius, sigma_color, sigma_time))
+            while len(_STABILIZE_TABLES) > _STABILIZE_TABLES_MAX:
+                _STABILIZE_TABLES.popitem(last=False)
+        else:
+            _STABILIZE_TABLES.move_to_end(key)
+    for t in tabs:                       # an evicted table may still be read by a launch on this stream: tell the allocator
+        t.record_stream(torch.cuda.current_stream(device))
+    return tabs
+
+
+def temporal_joint_bilateral_u16(depth_u16, guide_u8, radius, wt, wc, first, count, lo, hi, out=None):
+    """The temporal joint bilateral filter (ds_temporal_joint_bilateral_u16, include/depthstereo.h): depth uint16 cuda [m,h,w] contiguous,
+    guide uint8 cuda [m,h,w,3 or 4] contiguous (any byte alignment) -> uint16 [count,h,w], frames first .. first + count - 1 filtered over
+    the frames within `radius` of each that lie in lo..hi.  wt, wc: float64 cuda tensors of radius + 1 and 766 values
+    (stabilize_tables_on).  out: write into this contiguous uint16 tensor of that shape (it must not overlap depth)."""
+    torch = require_gpu()
+    if not (torch.is_tensor(depth_u16) and depth_u16.is_cuda and depth_u16.dtype == torch.uint16 and depth_u16.dim() == 3
+            and depth_u16.is_contiguous()):
+        raise DepthStereoError("temporal_joint_bilateral_u16: depth must be a contiguous uint16 cuda tensor [m,h,w], got %s %s"
+                               % (getattr(depth_u16, "dtype", type(depth_u16)), tuple(getattr(depth_u16, "shape", ()))))
+    if not (torch.is_tensor(guide_u8) and guide_u8.is_cuda and guide_u8.dtype == torch.uint8 and guide_u8.dim() == 4
+            and guide_u8.device == depth_u16.device and tuple(guide_u8.shape[:3]) == tuple(depth_u16.shape) and guide_u8.shape[3] in (3, 4)
+            and guide_u8.is_contiguous()):
+        raise DepthStereoError("temporal_joint_bilateral_u16: guide must be a contiguous uint8 cuda tensor [m,h,w,3 or 4] on the depth's "
+                               "device and of its size %s, got %s %s" % (tuple(depth_u16.shape), getattr(guide_u8, "dtype", type(guide_u8)),
+                                                                         tuple(getattr(guide_u8, "shape", ()))))
+    radius = int(radius)
+    for name, t, n in (("wt", wt, radius + 1), ("wc", wc, 766)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.device == depth_u16.device and t.dtype == torch.float64 and t.dim() == 1
+                and t.numel() == n and t.is_contiguous()):
+            raise DepthStereoError("temporal_joint_bilateral_u16: %s must be a contiguous float64 tensor of %d values on the depth's device"
+                                   % (name, n))
+    m, h, w = depth_u16.shape
+    shape = (max(int(count), 0), h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint16, device=depth_u16.device)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.device == depth_u16.device and out.dtype == torch.uint16
+              and tuple(out.shape) == shape and out.is_contiguous()):
+        raise DepthStereoError("temporal_joint_bilateral_u16: out must be a contiguous uint16 %s tensor on the depth's device" % (shape,))
+    CALLS["ds_temporal_joint_bilateral_u16"] += 1
+    _check(lib().ds_temporal_joint_bilateral_u16(ctx_for(_dev_index(depth_u16)), depth_u16.data_ptr(), guide_u8.data_ptr(), guide_u8.shape[3],
+                                                 m, h, w, radius, wt.data_ptr(), wc.data_ptr(), int(first), int(count), int(lo), int(hi),
+                                                 out.data_ptr(), _stream(depth_u16)))
     return out
 
 

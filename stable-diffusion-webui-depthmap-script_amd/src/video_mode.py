@@ -17,7 +17,9 @@ What is built: the COMPUTE of video mode on frame tensors --
   * scene cuts, the reference's TODO at :114 ("Detect cuts and process segments separately"): ``cut_scores`` / ``detect_cuts``
     compare the luma histograms of neighbouring frames (csrc/ds_video.hip on the device, torch.bincount on the host, sharded: one
     all-gather of 1 KB per frame), and ``cuts=`` on the three functions above normalises every scene as the reference normalises a
-    clip.  The 5-tap filter of float32 device frames is a kernel of the same file (DS_VIDEO_SMOOTH=0: torch passes).
+    clip.  The 5-tap filter of float32 device frames is a kernel of the same file (DS_VIDEO_SMOOTH=0: torch passes);
+  * ``stabilize_depth`` / ``stabilize_depth_sharded`` / ``gen_frames_sharded(stabilize=)``: a motion-adaptive temporal filter of the
+    uint16 depth guided by the frames (not in the reference; a third kernel of that file), off by default.
 Container I/O (moviepy / imageio-ffmpeg / av: open_path_as_images :13-64, frames_to_video :67-100) is outside the hot
 path and not built; callers hand in decoded frames.
 """
@@ -379,9 +381,172 @@ def detect_cuts(frames_u8, threshold=0.4, min_len=1, bins=64, group=None):
     return _cuts_from_scores(cut_scores(frames_u8, bins, group), threshold, min_len)
 
 
+# ---- temporal depth filter ------------------------------------------------------------------------------------------------------
+# Not in the reference: every frame is predicted on its own, and neither smoothening mode changes a frame relative to its neighbours
+# ('experimental' only finds its two percentiles on smoothed frames), so the depth of a static wall moves from frame to frame by the
+# network's noise and the stereo warp turns that into horizontal jitter.  The filter is a joint bilateral filter ALONG TIME of the
+# uint16 depth guided by the frames; the comment of ds_temporal_joint_bilateral_u16 in include/depthstereo.h is the definition, the
+# kernel is in csrc/ds_video.hip, and tests/video_stabilize_cases.py is its float64 NumPy model.
+# params = (radius, sigma_color, sigma_time): radius 1..4 frames on each side; sigma_color in units of SUMMED 8-bit channel difference
+# |dR| + |dG| + |dB| (0..765) of the same pixel in two frames; sigma_time in frames.  (2, 12.0, 1.5) is a mild setting, (4, 12.0, 2.5) a
+# strong one: starting points, not measured optima.
+def _stabilize_params(params, who):
+    from . import _native
+    try:
+        return _native.stabilize_params(params)
+    except ValueError as e:
+        raise _native.DepthStereoError('%s: %s' % (who, e)) from None
+
+
+def _stabilize_check(frames, depth, who):
+    import torch
+    from . import _native
+    if not (torch.is_tensor(depth) and depth.dtype == torch.uint16 and depth.dim() == 3):
+        raise _native.DepthStereoError('%s: depth must be uint16 [F,H,W] (the filter is defined on, and returns, uint16 levels), got %s %s'
+                                       % (who, getattr(depth, 'dtype', type(depth)), tuple(getattr(depth, 'shape', ()))))
+    if not (torch.is_tensor(frames) and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] in (3, 4)):
+        raise _native.DepthStereoError('%s: frames must be uint8 [F,H,W,3] or [F,H,W,4], got %s %s'
+                                       % (who, getattr(frames, 'dtype', type(frames)), tuple(getattr(frames, 'shape', ()))))
+    if tuple(frames.shape[:3]) != tuple(depth.shape) or frames.device != depth.device:
+        raise _native.DepthStereoError('%s: frames %s on %s and depth %s on %s must agree in [F,H,W] and device'
+                                       % (who, tuple(frames.shape), frames.device, tuple(depth.shape), depth.device))
+    if depth.shape[1] == 0 or depth.shape[2] == 0:
+        raise _native.DepthStereoError('%s: empty frames %s' % (who, tuple(depth.shape)))
+
+
+def _stabilize_torch(depth, guide, radius, wt, wc, first, count, lo, hi):
+    """ds_temporal_joint_bilateral_u16 as float64 torch ops on the tensors' device, operation for operation (the route CPU tensors take,
+    and the torch side of tools/video_stabilize_ab.py): for every tap u in increasing order, over the output frames whose tap lies in
+    lo..hi, one rounded product wt * wc[k], the product with the depth rounded, then the two sums; one tensor-by-tensor division,
+    torch.round (half to even).  Same bits as the kernel."""
+    import torch
+    h, w = depth.shape[1:]
+    num = torch.zeros((count, h, w), dtype=torch.float64, device=depth.device)
+    den = torch.zeros((count, h, w), dtype=torch.float64, device=depth.device)
+    rgb = guide[..., :3].to(torch.int16)
+    for u in range(-radius, radius + 1):
+        a, b = max(first, lo - u), min(first + count - 1, hi - u)            # the outputs i whose tap i + u lies in lo..hi
+        if a > b:
+            continue
+        k = (rgb[a + u:b + u + 1] - rgb[a:b + 1]).abs().sum(dim=3, dtype=torch.int64)
+        wgt = wt[abs(u)] * wc[k]
+        num[a - first:b - first + 1] += wgt * depth[a + u:b + u + 1].to(torch.float64)
+        den[a - first:b - first + 1] += wgt
+    return torch.round(num / den).to(torch.uint16)
+
+
+def stabilize_depth_sharded(local_frames, local_depth, params, group=None, cuts=None):
+    """stabilize_depth for frames sharded in CONTIGUOUS blocks over the ranks (multigpu.my_shard): local_frames uint8 [n_local,H,W,3|4]
+    and local_depth uint16 [n_local,H,W], torch tensors of one device -> uint16 [n_local,H,W], bit for bit the rows stabilize_depth
+    gives on the gathered clip, for every split.
+    Halo: every rank publishes its first and last min(n_local, radius) frames of BOTH tensors as bytes (the collectives have no 16-bit
+    integers) in one fixed-shape buffer, zero placeholders where it holds fewer, so an empty shard takes part too (one all-gather of
+    the counts, one of the buffer), and walks outwards over its neighbours until it has `radius` frames on each side or runs out of
+    ranks.  A side that runs out simply ends: those taps lie outside the clip and are omitted, nothing is replicated.  cuts: GLOBAL
+    frame indices, the same list on every rank; per scene the filter's lo / hi are the scene's bounds intersected with what this rank
+    holds.  One launch per scene of which the rank holds a frame (CPU tensors: the float64 torch route)."""
+    import torch
+    import torch.distributed as dist
+    radius, sigma_color, sigma_time = _stabilize_params(params, 'stabilize_depth_sharded')
+    _stabilize_check(local_frames, local_depth, 'stabilize_depth_sharded')
+    multi = _is_multi(group)
+    cuts = list(cuts) if cuts is not None else []
+    n_local = local_depth.shape[0]
+    counts = _shard_counts(n_local, local_depth.device, group)
+    rank = dist.get_rank(group) if multi else 0
+    world = dist.get_world_size(group) if multi else 1
+    start, total = sum(counts[:rank]), sum(counts)
+    if cuts:
+        _check_cuts(cuts, total)
+    local_frames, local_depth = local_frames.contiguous(), local_depth.contiguous()
+    before_f, before_d, after_f, after_d = [], [], [], []
+    if multi:
+        h, w, c = local_frames.shape[1:]
+        fb, db = h * w * c, h * w * 2                                       # bytes of one frame and of its depth
+        k = min(n_local, radius)
+        halo = torch.zeros((2, radius, fb + db), dtype=torch.uint8, device=local_depth.device)      # [0]: head, [1]: tail
+        if k:
+            halo[0, :k, :fb] = local_frames[:k].reshape(k, fb)                                        # left aligned
+            halo[0, :k, fb:] = local_depth[:k].view(torch.uint8).reshape(k, db)
+            halo[1, radius - k:, :fb] = local_frames[n_local - k:].reshape(k, fb)                     # right aligned
+            halo[1, radius - k:, fb:] = local_depth[n_local - k:].view(torch.uint8).reshape(k, db)
+        halos = [torch.empty_like(halo) for _ in range(world)]
+        dist.all_gather(halos, halo, group=group)
+        got = 0
+        for r in range(rank - 1, -1, -1):
+            take = min(counts[r], radius, radius - got)
+            if take:
+                rows = halos[r][1, radius - take:]
+                before_f.insert(0, rows[:, :fb].reshape(take, h, w, c))
+                before_d.insert(0, rows[:, fb:].contiguous().view(torch.uint16).reshape(take, h, w))
+                got += take
+            if got >= radius:
+                break
+        got = 0
+        for r in range(rank + 1, world):
+            take = min(counts[r], radius, radius - got)
+            if take:
+                rows = halos[r][0, :take]
+                after_f.append(rows[:, :fb].reshape(take, h, w, c))
+                after_d.append(rows[:, fb:].contiguous().view(torch.uint16).reshape(take, h, w))
+                got += take
+            if got >= radius:
+                break
+    out = torch.empty_like(local_depth)
+    if n_local == 0:
+        return out
+    if before_f or after_f:                                                # ext[0] is global frame start - off
+        ext_f = torch.cat(before_f + [local_frames] + after_f).contiguous()
+        ext_d = torch.cat(before_d + [local_depth] + after_d).contiguous()
+    else:
+        ext_f, ext_d = local_frames, local_depth
+    off = sum(t.shape[0] for t in before_d)
+    m = ext_d.shape[0]
+    from . import _native
+    wt, wc = _native.stabilize_tables_on(local_depth.device, radius, sigma_color, sigma_time)
+    for g0, g1, ls, le in _segments(cuts, start, n_local, total):
+        if le == ls:
+            continue
+        lo, hi = max(g0 - start + off, 0), min(g1 - 1 - start + off, m - 1)
+        if local_depth.is_cuda:
+            _native.temporal_joint_bilateral_u16(ext_d, ext_f, radius, wt, wc, ls + off, le - ls, lo, hi, out=out[ls:le])
+        else:
+            out[ls:le] = _stabilize_torch(ext_d, ext_f, radius, wt, wc, ls + off, le - ls, lo, hi)
+    return out
+
+
+def stabilize_depth(frames_u8, depth_u16, params, cuts=None):
+    """The temporal depth filter on a whole clip held by one device: frames_u8 uint8 [F,H,W,3|4] and depth_u16 uint16 [F,H,W], both
+    torch tensors (of one device) or both NumPy arrays -> uint16 [F,H,W] of the same kind.  params = (radius, sigma_color, sigma_time),
+    see above.  cuts: frame indices at which a new scene starts (detect_cuts makes such a list); nothing is averaged across one, and
+    a scene of one frame comes back unchanged.  Device tensors: ONE ds_temporal_joint_bilateral_u16 launch per scene; CPU tensors and
+    arrays: the same loop in float64 torch ops, the same bits.  A bad tuple, dtype or shape raises DepthStereoError and bad cuts
+    ValueError, before any launch."""
+    import torch
+    from . import _native
+    _stabilize_params(params, 'stabilize_depth')
+    as_numpy = isinstance(depth_u16, np.ndarray)
+    if as_numpy != isinstance(frames_u8, np.ndarray):
+        raise _native.DepthStereoError('stabilize_depth: frames and depth must both be torch tensors or both NumPy arrays, got %s and %s'
+                                       % (type(frames_u8).__name__, type(depth_u16).__name__))
+    if as_numpy:
+        if depth_u16.dtype != np.uint16 or frames_u8.dtype != np.uint8:
+            raise _native.DepthStereoError('stabilize_depth: frames must be uint8 and depth uint16, got %s and %s'
+                                           % (frames_u8.dtype, depth_u16.dtype))
+        frames_u8, depth_u16 = torch.from_numpy(np.ascontiguousarray(frames_u8)), torch.from_numpy(np.ascontiguousarray(depth_u16))
+    _stabilize_check(frames_u8, depth_u16, 'stabilize_depth')
+    if cuts:
+        _check_cuts(cuts, depth_u16.shape[0])
+    out = stabilize_depth_sharded(frames_u8, depth_u16, params, group=_LOCAL, cuts=cuts)
+    return out.numpy() if as_numpy else out
+
+
 def gen_frames_sharded(frames_u8, predict_batch, inp, smoothening='none', group=None, batch=8, dst=0, invert=False,
-                       cuts=None, cut_threshold=0.4, cut_min_len=1):
+                       cuts=None, cut_threshold=0.4, cut_min_len=1, stabilize=None):
     """Two-pass video pipeline on decoded frames, frame parallel.
+    stabilize: None -- nothing is added (no launch, no collective, no copy); (radius, sigma_color, sigma_time) -- the temporal depth
+    filter (stabilize_depth_sharded) runs on the uint16 depth between the quantisation and the stereo warp, with the cuts of this call,
+    and 'depth' in the result is the filtered map.  A bad tuple raises DepthStereoError before the first pass.
     cuts: None -- the clip is one scene; 'auto' -- detect_cuts(threshold=cut_threshold, min_len=cut_min_len) on the decoded frames,
     each rank on its own block; a list -- used as given.  With cuts the result on rank `dst` also has the key 'cuts' (the list).
     frames_u8: uint8 tensor [F, H, W, 3] (every rank may hold the full clip or just index its block); predict_batch:
@@ -394,6 +559,8 @@ def gen_frames_sharded(frames_u8, predict_batch, inp, smoothening='none', group=
     import torch.distributed as dist
     from . import _native, multigpu
     from .stereoimage_generation import create_stereoimages_batch
+    if stabilize is not None:
+        stabilize = _stabilize_params(stabilize, 'gen_frames_sharded')
     multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
     rank = dist.get_rank(group) if multi else 0
     world = dist.get_world_size(group) if multi else 1
@@ -418,6 +585,8 @@ def gen_frames_sharded(frames_u8, predict_batch, inp, smoothening='none', group=
         d16 = _native.convert_to_i16(norm.double().contiguous())
     else:
         d16 = torch.empty((0,) + tuple(frames_u8.shape[1:3]), dtype=torch.uint16, device=dev)
+    if stabilize is not None:                                                                     # every rank, also one without frames
+        d16 = stabilize_depth_sharded(mine, d16, stabilize, group=group, cuts=cuts)
     modes = list(inp.get('stereo_modes', ['left-right']))
     outs = {'depth': d16}
     if inp.get('gen_stereo', True) and e > s:                                                     # pass 2 (:160)
