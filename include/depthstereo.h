@@ -722,6 +722,25 @@ int ds_upsample_bilinear_nhwc(ds_ctx *ctx, const void *in, void *out, int batch,
                               int out_h, int out_w, int align_corners, int dtype, void *stream);
 
 /*
+ * ds_dpt_head_front -- the front of the DPT depth heads in one kernel: refinenet1's final bilinear upsample (align_corners=True)
+ * and the head's first convolution (dmidas/dpt_depth.py:150 output_conv[0] behind dmidas/blocks.py:429-431;
+ * ddepth_anything_v2/depth_anything_v2/dpt.py:146 output_conv1 behind util/blocks.py:141-145):
+ *     out = conv3x3(upsample_bilinear(x, (out_h, out_w), align_corners=True), w, zero padding 1) + bias
+ *   x     [batch, in_h, in_w, in_channels] f16/bf16, channels_last
+ *   w     [out_channels][tap = ky * 3 + kx][in_channels], same dtype: what ds_conv3x3_nhwc takes;  bias [out_channels], same dtype, or NULL
+ *   out   [batch, out_h, out_w, out_channels], same dtype; nothing outside it is written
+ * The upsampled map exists only tile by tile in LDS.  The result is BIT-IDENTICAL to ds_upsample_bilinear_nhwc followed by
+ * ds_conv3x3_nhwc (act 0, no residual operands): an upsampled value is that kernel's expression (four rounded float32 products added
+ * left to right, one rounding), the halo outside the upsampled image is literal zeros, and an output element's float32 chain is the
+ * convolution's term for term (64-channel chunks ascending, taps 0..8 inside a chunk, four 32x32x16 MFMAs per tap, then + bias and
+ * one rounding).  Built for out_channels == 128 and in_channels % 64 == 0 (<= 4096), and for upsample factors whose source pixels
+ * under a 10 x 34 patch fit 6 x 18 (a factor of exactly 2 always does); everything else returns DS_EUNSUPPORTED and the caller runs the two
+ * launches.  Allocates nothing and synchronises nothing: capturable in a hipGraph.  out must not alias x.
+ */
+int ds_dpt_head_front(ds_ctx *ctx, const void *x, const void *w, const void *bias, void *out, int batch, int in_h, int in_w,
+                      int out_h, int out_w, int in_channels, int out_channels, int dtype, void *stream);
+
+/*
  * ds_dpt_head_tail -- the tail of the DPT depth heads in one kernel: bilinear upsample (align_corners=True) ->
  * conv3x3 128->32 (padding 1) -> ReLU -> conv1x1 32->1 -> optional ReLU (dmidas/dpt_depth.py:150-158 output_conv[1:6];
  * ddepth_anything_v2/depth_anything_v2/dpt.py:146-147 with output_conv2 :105-111).

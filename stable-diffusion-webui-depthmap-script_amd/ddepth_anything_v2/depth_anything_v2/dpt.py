@@ -32,7 +32,8 @@ class FeatureFusionBlock(nn.Module):
         self.resConfUnit1 = ResidualConvUnit(features)
         self.resConfUnit2 = ResidualConvUnit(features)
 
-    def forward(self, *xs, size=None):  # blocks.py:121-148 (align_corners=True)
+    def forward(self, *xs, size=None, upsample=True):  # blocks.py:121-148 (align_corners=True)
+        """upsample=False: the low-resolution out_conv result, for a caller that fuses the final x2 upsample into what follows."""
         output = xs[0]
         if len(xs) == 2:                # skip add fused into the unit's last element-wise pass
             output = vm.residual_conv_unit(self.resConfUnit1.conv1, self.resConfUnit1.conv2, xs[1], skip=output)
@@ -40,6 +41,8 @@ class FeatureFusionBlock(nn.Module):
         # the reference interpolates, then applies the 1x1 out_conv; both are linear and the bilinear weights sum to one,
         # so they commute (bias included): the conv runs on 4x fewer pixels and the upsample writes the final tensor
         output = vm.conv_module(self.out_conv, output)
+        if not upsample:
+            return output
         if size is None:
             return vm.interpolate_bilinear(output, scale_factor=2, align_corners=True)
         return vm.interpolate_bilinear(output, size=tuple(size), align_corners=True)
@@ -86,8 +89,13 @@ class DPTHead(nn.Module):
         path_4 = s.refinenet4(l4, size=l3.shape[2:])
         path_3 = s.refinenet3(path_4, l3, size=l2.shape[2:])
         path_2 = s.refinenet2(path_3, l2, size=l1.shape[2:])
-        path_1 = s.refinenet1(path_2, l1)
-        out = vm.conv2d(s.output_conv1, path_1)                # 256 -> 128: the in-tree implicit GEMM (256 x 128 tiles) where it fills the chip
+        if vm.head_front_ok(l1, s.output_conv1):
+            # refinenet1's x2 upsample + output_conv1 in one kernel (ds_dpt_head_front): the upsampled map is never written
+            from src import _native
+            out = _native.dpt_head_front(s.refinenet1(path_2, l1, upsample=False), s.output_conv1)
+        else:
+            path_1 = s.refinenet1(path_2, l1)
+            out = vm.conv2d(s.output_conv1, path_1)            # 256 -> 128: the in-tree implicit GEMM (256 x 128 tiles) where it fills the chip
         size = (int(patch_h * 14), int(patch_w * 14))
         if (vm.half_on_gpu(out) and tuple(s.output_conv2[0].weight.shape) == (32, 128, 3, 3)
                 and s.output_conv2[0].padding_mode in ('zeros', 'circular') and vm.circular_hip_ok(s.output_conv2[0])):

@@ -36,13 +36,16 @@ class FeatureFusionBlock_custom(nn.Module):
         self.resConfUnit1 = ResidualConvUnit_custom(features)
         self.resConfUnit2 = ResidualConvUnit_custom(features)
 
-    def forward(self, *xs, size=None):  # blocks.py:412-441, align_corners=True
+    def forward(self, *xs, size=None, upsample=True):  # blocks.py:412-441, align_corners=True
+        """upsample=False: the low-resolution out_conv result, for a caller that fuses the final x2 upsample into what follows."""
         output = xs[0]
         if len(xs) == 2:                # skip add fused into the unit's last element-wise pass
             output = vm.residual_conv_unit(self.resConfUnit1.conv1, self.resConfUnit1.conv2, xs[1], skip=output)
         output = self.resConfUnit2(output)
         # 1x1 out_conv and bilinear interpolation commute (linear, weights sum to one): conv first, on 4x fewer pixels
         output = vm.conv_module(self.out_conv, output)
+        if not upsample:
+            return output
         if size is None:
             return vm.interpolate_bilinear(output, scale_factor=2, align_corners=True)
         return vm.interpolate_bilinear(output, size=tuple(size), align_corners=True)
@@ -95,8 +98,15 @@ class DPT(nn.Module):
         path_4 = s.refinenet4(l4, size=l3.shape[2:])
         path_3 = s.refinenet3(path_4, l3, size=l2.shape[2:])
         path_2 = s.refinenet2(path_3, l2, size=l1.shape[2:])
-        path_1 = s.refinenet1(path_2, l1)
         head = s.output_conv
+        # (l1 has path_1's device and dtype, and the shape of refinenet1's out_conv result: the routes are decided before refinenet1 runs)
+        tail_hip = (vm.half_on_gpu(l1) and isinstance(head[1], Interpolate)
+                    and head[1].mode == "bilinear" and head[1].align_corners and tuple(head[2].weight.shape) == (32, 128, 3, 3)
+                    and head[2].padding_mode in ('zeros', 'circular') and vm.circular_hip_ok(head[2]))
+        # refinenet1's x2 upsample + the head's 256 -> 128 convolution in one kernel (ds_dpt_head_front): the upsampled map is never
+        # written.  Not with taps (ZoeDepth needs path_1 itself), TILING_MODE, float32 or on the CPU: head_front_ok says no.
+        front_hip = features is None and tail_hip and vm.head_front_ok(l1, head[0])
+        path_1 = s.refinenet1(path_2, l1, upsample=not front_hip)
         if features is not None:
             features.update(l4_rn=l4, r4=path_4, r3=path_3, r2=path_2, r1=path_1)
             y = path_1
@@ -105,15 +115,16 @@ class DPT(nn.Module):
                 if i == 3:
                     features['out_conv'] = y
             return y
-        if (vm.half_on_gpu(path_1) and isinstance(head[1], Interpolate)
-                and head[1].mode == "bilinear" and head[1].align_corners and tuple(head[2].weight.shape) == (32, 128, 3, 3)
-                and head[2].padding_mode in ('zeros', 'circular') and vm.circular_hip_ok(head[2])):
+        if tail_hip:
             # (TILING_MODE makes the convolutions circular: ds_dpt_head_tail_circular; DS_CONV_CIRCULAR=0: the torch sequence below)
             # upsample x2 -> conv3x3 128->32 -> ReLU -> conv1x1 -> ReLU in one MFMA kernel (ds_dpt_head_tail)
             from src import _native
             # the head's first convolution (256 -> 128): the in-tree implicit GEMM on 256 x 128 tiles where the launch fills the chip
             # (round 4; MIOpen's heuristic choice for it varied from 1.75 to 2.1 ms per 32 x 256^2 between boxes), else the library
-            y = vm.conv2d(head[0], path_1) if vm.conv3x3_hip_ok(head[0], path_1) else vm.conv_module(head[0], path_1)
+            if front_hip:
+                y = _native.dpt_head_front(path_1, head[0])                # path_1 is still the low-resolution map here
+            else:
+                y = vm.conv2d(head[0], path_1) if vm.conv3x3_hip_ok(head[0], path_1) else vm.conv_module(head[0], path_1)
             size = (int(y.shape[2] * head[1].scale_factor), int(y.shape[3] * head[1].scale_factor))
             return _native.dpt_head_tail(y, size, head[2], head[4], relu_out=isinstance(head[5], nn.ReLU))
         return head(path_1)

@@ -28,7 +28,7 @@ EXPORTS = [
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
     "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
-    "ds_preprocess_bicubic_rows", "ds_tokens_fixup", "ds_upsample_bicubic_to_f32", "ds_im2col3x3_s2_nhwc",
+    "ds_preprocess_bicubic_rows", "ds_tokens_fixup", "ds_upsample_bicubic_to_f32", "ds_im2col3x3_s2_nhwc", "ds_dpt_head_front",
 ]
 
 
@@ -53,7 +53,8 @@ _lib_lock = threading.Lock()
 # really took the in-tree kernels it claims: a routing threshold that silently sends a shape to the library shows up here).
 # ds_linear_qkv runs two of the counted GEMMs in one launch: it counts under its own name AND once under ds_linear and ds_linear_vt,
 # so "how many Q/K and V^T GEMMs ran in-tree" reads the same on either route; ds_linear_qkv alone tells the routes apart.
-# ds_linear_rows4 likewise: its own name once, and ds_linear once per GEMM it carries; ds_conv3x3_nhwc_pair: ds_conv3x3_nhwc twice.
+# ds_linear_rows4 likewise: its own name once, and ds_linear once per GEMM it carries; ds_conv3x3_nhwc_pair: ds_conv3x3_nhwc twice;
+# ds_dpt_head_front: ds_upsample_bilinear_nhwc and ds_conv3x3_nhwc once each.
 CALLS = collections.Counter()
 
 
@@ -101,6 +102,7 @@ def lib():
             L.ds_upsample_bilinear_nhwc.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
             L.ds_dpt_head_tail.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, ctypes.c_float, ci, vp, ci, vp]
             L.ds_dpt_head_tail_circular.argtypes = L.ds_dpt_head_tail.argtypes
+            L.ds_dpt_head_front.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
             L.ds_preprocess_bicubic.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_float),
                                                 ctypes.POINTER(ctypes.c_float), ci, vp]
             L.ds_preprocess_bicubic_rows.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_float),
@@ -1512,6 +1514,39 @@ def upsample_bilinear(x, size=None, scale_factor=None, align_corners=True):
     CALLS["ds_upsample_bilinear_nhwc"] += 1
     _check(lib().ds_upsample_bilinear_nhwc(ctx_for(_dev_index(x)), xin.data_ptr(), out.data_ptr(), b, c, ih, iw, oh, ow,
                                            1 if align_corners else 0, 1 if x.dtype == torch.float16 else 2, _stream(x)))
+    return out
+
+
+def dpt_head_front_supported(x, conv):
+    """What ds_dpt_head_front takes: a zero-padded 3x3, stride-1 nn.Conv2d with 128 output channels and in % 64 == 0 on an NCHW-shaped
+    activation with that many channels.  (The x2, align_corners upsample it fuses always fits the kernel's staging tile.)"""
+    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1)
+            and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros'
+            and conv.out_channels == 128 and conv.in_channels % 64 == 0 and conv.in_channels <= 4096
+            and x.dim() == 4 and x.shape[1] == conv.in_channels and x.numel() > 0)
+
+
+def dpt_head_front(x, conv, out=None):
+    """conv(upsample_bilinear(x, scale_factor=2, align_corners=True)) for the head's first convolution (3x3, 256 -> 128) in one kernel
+    (include/depthstereo.h: ds_dpt_head_front): the upsampled map is never written.  Bit-identical to conv3x3(conv,
+    upsample_bilinear(x, scale_factor=2)).  x: NCHW-shaped float16 / bfloat16 CUDA tensor (channels_last is zero-copy); returns a
+    channels_last [B, 128, 2h, 2w] tensor (out: a caller-owned NHWC buffer of that many elements, for tests)."""
+    torch = require_gpu()
+    assert x.is_cuda and x.dtype in (torch.float16, torch.bfloat16) and dpt_head_front_supported(x, conv)
+    x = x.contiguous(memory_format=torch.channels_last)
+    b, c, ih, iw = x.shape
+    oh, ow = 2 * ih, 2 * iw
+    wk, bk = _conv_weight_image(conv, x.dtype)
+    if out is None:
+        out = torch.empty((b, conv.out_channels, oh, ow), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    else:
+        assert out.is_cuda and out.dtype == x.dtype and out.is_contiguous() and out.numel() == b * oh * ow * conv.out_channels
+    CALLS["ds_dpt_head_front"] += 1
+    CALLS["ds_upsample_bilinear_nhwc"] += 1
+    CALLS["ds_conv3x3_nhwc"] += 1
+    _check(lib().ds_dpt_head_front(ctx_for(_dev_index(x)), x.data_ptr(), wk.data_ptr(), None if bk is None else bk.data_ptr(),
+                                   out.data_ptr(), b, ih, iw, oh, ow, c, conv.out_channels,
+                                   1 if x.dtype == torch.float16 else 2, _stream(x)))
     return out
 
 

@@ -558,6 +558,23 @@ def conv3x3_hip_ok(conv, x):
 
 
 CONV_PAIR = os.environ.get("DS_CONV_PAIR", "1") != "0"          # A/B switch: two small 3x3 convolutions in one launch = ds_conv3x3_nhwc_pair
+# A/B switch: refinenet1's x2 upsample and the head's 256 -> 128 convolution in one kernel = ds_dpt_head_front (0 = the two launches,
+# bit-identical).  Off inside library_routing() and stock_routing(): there the convolution is not the in-tree one.
+HEAD_FRONT = os.environ.get("DS_HEAD_FRONT", "1") != "0"
+
+
+def head_front_ok(x, conv, scale_factor=2, align_corners=True):
+    """True where conv(interpolate_bilinear(x, scale_factor, align_corners)) runs as ds_dpt_head_front: x is the LOW-resolution
+    half-precision activation on the GPU, the upsample is x2 with align_corners, conv is the heads' zero-padded (128, 256, 3, 3)
+    convolution, and the two launches it replaces would both be the in-tree kernels (so the bits do not move)."""
+    if not (HEAD_FRONT and CONV_HIP and CONV_HEAD_HIP and half_on_gpu(x) and x.dim() == 4 and type(conv) is nn.Conv2d):
+        return False
+    if scale_factor != 2 or not align_corners or tuple(conv.weight.shape) != (128, 256, 3, 3):
+        return False
+    from . import _native
+    pixels = x.shape[0] * 2 * x.shape[2] * 2 * x.shape[3]                  # of the upsampled map: what conv3x3_hip_ok would see
+    return (_native.dpt_head_front_supported(x, conv) and pixels >= 256
+            and (pixels + 255) // 256 >= (1 if invariant() else CONV_HIP_MIN_TILES))
 
 
 def conv2d_pair(conv0, x0, conv1, x1):
