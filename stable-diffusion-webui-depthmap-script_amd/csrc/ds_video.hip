@@ -42,18 +42,17 @@
 //   they are issued.
 //     * The guide is read byte by byte, three loads per pixel and frame: with c == 3 and an odd plane every frame sits at another
 //       byte alignment, and the base may be any address.  A wave's three loads cover the same 192 (256) contiguous bytes, so the
-//       second and third hit the lines the first brought in; k is then ONE v_sad_u8 of two packed words, as in ds_joint_bilateral.hip.
-//     * wc (766 float64) is indexed PER LANE by k.  It is staged in LDS (6 KiB) once per workgroup, as ds_joint_bilateral.hip does: a
+//       second and third hit the lines the first brought in; k is then ONE v_sad_u8 of two packed words (ds_bilateral.h).
+//     * wc (DS_BL_WC float64) is indexed PER LANE by k.  It is staged in LDS (6 KiB) once per workgroup, as the guided spatial kernel does: a
 //       per-lane gather from memory would cost one address per lane in the vector memory path for every tap, next to the frame
 //       loads the kernel lives on; in LDS it is one ds_read_b64 whose lanes mostly ask for the same few small k on static content
 //       (broadcast) and spread over the 32 bank pairs on moving content.  wt (R + 1 values, the same for every lane) is read once
 //       into registers.
-//     * Arithmetic per tap: wt * wc, the product with the depth, two sums, all float64 and each rounded on its own (contraction is
-//       off, see above); one IEEE division and v_rndne_f64 per output.
+//     * Arithmetic per tap and the finish of an output: the family's (ds_bl_tap, ds_bl_finish_u16 of ds_bilateral.h).
 //     * Short clips of small frames: when the pixels alone give fewer than TJ_MIN_BLOCKS workgroups, the outputs are split into
 //       chunks of at least TJ_MIN_CHUNK frames over grid.y and every chunk primes its own window (2 R more frame reads per chunk).
 //       A pixel's chain of operations is the same in every chunking, so the bits do not depend on it.
-#include "ds_common.h"
+#include "ds_bilateral.h"
 
 #pragma clang fp contract(off)
 
@@ -219,14 +218,8 @@ DS_API int ds_temporal_smooth5_f32(ds_ctx *ctx, const float *src, int m, int64_t
 // ---- temporal joint bilateral filter ------------------------------------------------------------------------------------------------
 #define TJ_THREADS 256
 #define TJ_PPT 2
-#define TJ_WC 766                   // 3 * 255 + 1 colour differences
 #define TJ_MIN_BLOCKS 1024          // below this many workgroups from the pixels alone, the time axis is split over grid.y
 #define TJ_MIN_CHUNK 8              // ... into chunks of at least this many output frames
-
-__device__ __forceinline__ uint32_t tj_rgb(const uint8_t *px)      // three byte loads: any alignment, the fourth byte never read
-{
-    return (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16);
-}
 
 template <int R>
 __global__ __launch_bounds__(TJ_THREADS) void k_temporal_joint_bilateral_u16(const uint16_t *__restrict__ depth, const uint8_t *__restrict__ guide,
@@ -235,8 +228,8 @@ __global__ __launch_bounds__(TJ_THREADS) void k_temporal_joint_bilateral_u16(con
                                                                              uint16_t *__restrict__ out)
 {
     enum { W = 2 * R + 1 };
-    __shared__ double wc_lds[TJ_WC];
-    for (int i = threadIdx.x; i < TJ_WC; i += TJ_THREADS) wc_lds[i] = wc[i];
+    __shared__ double wc_lds[DS_BL_WC];
+    ds_bl_stage_wc(wc_lds, wc, threadIdx.x, TJ_THREADS);
     double t[R + 1];
 #pragma unroll
     for (int a = 0; a <= R; a++) t[a] = wt[a];
@@ -266,7 +259,7 @@ __global__ __launch_bounds__(TJ_THREADS) void k_temporal_joint_bilateral_u16(con
 #pragma unroll
         for (int e = 0; e < TJ_PPT; e++) {
             d[e][u] = dp[e][fo];
-            g[e][u] = tj_rgb(gp[e] + fo * gc);
+            g[e][u] = ds_bl_rgb(gp[e] + fo * gc);
         }
     }
     for (int j = j0; j < j1; j++) {
@@ -276,7 +269,7 @@ __global__ __launch_bounds__(TJ_THREADS) void k_temporal_joint_bilateral_u16(con
 #pragma unroll
             for (int e = 0; e < TJ_PPT; e++) {
                 dn[e] = dp[e][fo];
-                gn[e] = tj_rgb(gp[e] + fo * gc);
+                gn[e] = ds_bl_rgb(gp[e] + fo * gc);
             }
         }
         double num[TJ_PPT], den[TJ_PPT];
@@ -289,17 +282,12 @@ __global__ __launch_bounds__(TJ_THREADS) void k_temporal_joint_bilateral_u16(con
             // term is >= +0.0 and finite), so the chain has the bits it has without the tap -- and no branch splits the tap loop.
             const double tw = (s >= lo && s <= hi) ? t[u < R ? R - u : u - R] : 0.0;
 #pragma unroll
-            for (int e = 0; e < TJ_PPT; e++) {
-                // |R_s - R_i| + |G_s - G_i| + |B_s - B_i| (+ |0 - 0|): one v_sad_u8; 0..765, inside the table by construction
-                const double wgt = tw * wc_lds[__builtin_amdgcn_sad_u8(g[e][u], g[e][R], 0u)];
-                const double prod = wgt * (double)d[e][u];
-                num[e] = num[e] + prod;
-                den[e] = den[e] + wgt;
-            }
+            for (int e = 0; e < TJ_PPT; e++)
+                ds_bl_tap(tw, wc_lds[__builtin_amdgcn_sad_u8(g[e][u], g[e][R], 0u)], d[e][u], num[e], den[e]);
         }
 #pragma unroll
         for (int e = 0; e < TJ_PPT; e++) {
-            if (ok[e]) op[e][(int64_t)j * plane] = (uint16_t)(unsigned)__builtin_rint(num[e] / den[e]);      // v_rndne_f64: half to even
+            if (ok[e]) op[e][(int64_t)j * plane] = ds_bl_finish_u16(num[e], den[e]);
 #pragma unroll
             for (int u = 0; u + 1 < W; u++) {
                 d[e][u] = d[e][u + 1];

@@ -315,101 +315,100 @@ def normalmap(depth, pre_blur, sobel_ksize, post_blur, invert, wrap=False):
     return out
 
 
-_BILATERAL_TABLES = collections.OrderedDict()          # (device index, d, sigma_color, sigma_space) -> (ws, wr) on that device
-_BILATERAL_TABLES_MAX = 4
-_BILATERAL_LOCK = threading.Lock()
+# ---- the bilateral family: the normal map's pre-filter and depth refinement (csrc/ds_bilateral.hip: one tile routine, two kernels), video
+# mode's temporal depth filter (csrc/ds_video.hip); csrc/ds_bilateral.h holds what the three kernels share.  Public interfaces:
+# src/normalmap_generation.py, src/depth_refine.py, src/video_mode.py --------------------------------------------------------------------
+_TABLES = collections.defaultdict(collections.OrderedDict)     # family -> {(device index, parameters ...): tensors on that device}, LRU
+_TABLES_LOCK = threading.Lock()
+DEPTH_REFINE_MAX_ITERATIONS = 8
+STABILIZE_MAX_RADIUS = 4
+
+
+def _tables_on(family, device, params, build, keep=4):
+    """build(*params) -- NumPy arrays -- as tensors on the cuda `device`: uploaded once and kept for the family's last `keep`
+    (device, params).  The family is part of the key: equal parameter tuples of two families name different tables, and a family
+    evicts only its own."""
+    torch = _torch()
+    device = torch.device(device)
+    key = (device.index if device.index is not None else torch.cuda.current_device(),) + tuple(params)
+    with _TABLES_LOCK:
+        lru = _TABLES[family]
+        tabs = lru.get(key)
+        if tabs is None:
+            tabs = lru[key] = tuple(torch.from_numpy(t).to(device) for t in build(*params))
+            while len(lru) > keep:
+                lru.popitem(last=False)
+        else:
+            lru.move_to_end(key)
+    for t in tabs:                   # an evicted table may still be read by a launch on this stream: tell the allocator
+        t.record_stream(torch.cuda.current_stream(device))
+    return tabs
+
+
+def cached_tables(family):
+    """How many (device, params) the table cache holds for `family`: "bilateral", "depth_refine", "stabilize" or "lanczos"."""
+    with _TABLES_LOCK:
+        return len(_TABLES[family])
+
+
+def _as_int(v):
+    """(int(v), whether v IS that integer and no bool, Python's or NumPy's).  Raises what int(v) raises."""
+    return int(v), not isinstance(v, (bool, np.bool_)) and int(v) == v
+
+
+def _filter_params(name, usage, p, size, lo, hi, odd, sigmas, max_iterations=None):
+    """The validator behind bilateral_params, depth_refine_params and stabilize_params.  p: (size, sigma, sigma) or -- where
+    max_iterations is given -- (size, sigma, sigma, iterations); returns it as (int, float, float[, int]) or raises ValueError:
+    size an integer in lo..hi (odd where `odd`), both sigmas finite and > 0, iterations an integer in 1..max_iterations (default
+    1); a bool is no integer.  `name`, `usage`, `size` and `sigmas` are the words of the messages."""
+    try:
+        if isinstance(p, (str, bytes)):
+            raise TypeError
+        q = tuple(p)
+        if len(q) not in ((3, 4) if max_iterations else (3,)):
+            raise TypeError
+        (n, ok_n), s0, s1 = _as_int(q[0]), float(q[1]), float(q[2])
+        it, ok_it = _as_int(q[3]) if len(q) == 4 else (1, True)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s must be %s, got %r" % (name, usage, p)) from None
+    if not (ok_n and lo <= n <= hi and (n % 2 == 1 or not odd)):
+        raise ValueError("%s: %s must be an %sinteger in %d..%d, got %r" % (name, size, "odd " if odd else "", lo, hi, q[0]))
+    if not (0.0 < s0 < math.inf and 0.0 < s1 < math.inf):
+        raise ValueError("%s: %s and %s must be finite and > 0, got %r, %r" % (name, sigmas[0], sigmas[1], s0, s1))
+    if not max_iterations:
+        return n, s0, s1
+    if not (ok_it and 1 <= it <= max_iterations):
+        raise ValueError("%s: iterations must be an integer in 1..%d, got %r" % (name, max_iterations, q[3] if len(q) == 4 else it))
+    return n, s0, s1, it
 
 
 def bilateral_params(bilateral):
     """(d, sigma_color, sigma_space) as (int, float, float), or ValueError: d odd in 3..31, both sigmas finite and > 0.  Pure
     Python (the funnel checks its option with it before any device work)."""
-    try:
-        d, sigma_color, sigma_space = bilateral
-        ok = not isinstance(d, bool) and int(d) == d
-        d, sigma_color, sigma_space = int(d), float(sigma_color), float(sigma_space)
-    except (TypeError, ValueError, OverflowError):
-        raise ValueError("bilateral must be (d, sigma_color, sigma_space), got %r" % (bilateral,)) from None
-    if not (ok and d % 2 == 1 and 3 <= d <= 31):
-        raise ValueError("bilateral: d must be an odd integer in 3..31, got %r" % (bilateral[0],))
-    if not (0.0 < sigma_color < math.inf and 0.0 < sigma_space < math.inf):
-        raise ValueError("bilateral: sigma_color and sigma_space must be finite and > 0, got %r, %r" % (sigma_color, sigma_space))
-    return d, sigma_color, sigma_space
-
-
-def bilateral_tables(d, sigma_color, sigma_space):
-    """The two host-made tables of ds_bilateral_u16 (include/depthstereo.h), float64: ws (d * d, raster order, exactly 0 outside the
-    circle of radius d // 2) and wr (65536, indexed by the integer |D(q) - D(p)|)."""
-    r = d // 2
-    dy, dx = np.mgrid[-r:r + 1, -r:r + 1]
-    ws = np.where(dx * dx + dy * dy <= r * r, np.exp(-(dx * dx + dy * dy) / (2.0 * sigma_space**2)), 0.0).astype(np.float64).ravel()
-    wr = np.exp(-(np.arange(65536, dtype=np.float64)**2) / (2.0 * sigma_color**2))
-    return ws, wr
-
-
-def bilateral_u16(depth_u16, d, sigma_color, sigma_space, wrap=False):
-    """Bilateral filter of uint16 depth maps [n,h,w] (cuda) -> float64 [n,h,w] in the same units (ds_bilateral_u16: the definition is
-    in include/depthstereo.h).  d: odd window diameter 3..31; sigma_color in uint16 levels; sigma_space in pixels; wrap: tap indices
-    modulo the image size instead of BORDER_REFLECT_101 (which needs d // 2 < min(h, w)).  The tables are made on the host, uploaded
-    once and kept for the last 4 (device, d, sigma_color, sigma_space)."""
-    torch = require_gpu()
-    try:
-        d, sigma_color, sigma_space = bilateral_params((d, sigma_color, sigma_space))
-    except ValueError as e:
-        raise DepthStereoError("bilateral_u16: %s" % e) from None
-    if not (torch.is_tensor(depth_u16) and depth_u16.is_cuda and depth_u16.dtype == torch.uint16 and depth_u16.dim() == 3):
-        raise DepthStereoError("bilateral_u16: depth must be a uint16 cuda tensor [n,h,w] (the range table is indexed by an integer "
-                               "difference), got %s %s" % (getattr(depth_u16, "dtype", type(depth_u16)), tuple(getattr(depth_u16, "shape", ()))))
-    depth_u16 = depth_u16.contiguous()
-    n, h, w = depth_u16.shape
-    if not wrap and d // 2 >= min(h, w):
-        raise DepthStereoError("bilateral_u16: d // 2 = %d must be below min(h, w) = %d without wrap" % (d // 2, min(h, w)))
-    key = (_dev_index(depth_u16), d, sigma_color, sigma_space)
-    with _BILATERAL_LOCK:
-        tabs = _BILATERAL_TABLES.get(key)
-        if tabs is None:
-            ws, wr = bilateral_tables(d, sigma_color, sigma_space)
-            tabs = _BILATERAL_TABLES[key] = (torch.from_numpy(ws).to(depth_u16.device), torch.from_numpy(wr).to(depth_u16.device))
-            while len(_BILATERAL_TABLES) > _BILATERAL_TABLES_MAX:
-                _BILATERAL_TABLES.popitem(last=False)
-        else:
-            _BILATERAL_TABLES.move_to_end(key)
-    for t in tabs:                   # an evicted table may still be read by a launch on this stream: tell the allocator
-        t.record_stream(torch.cuda.current_stream(depth_u16.device))
-    out = torch.empty((n, h, w), dtype=torch.float64, device=depth_u16.device)
-    CALLS["ds_bilateral_u16"] += 1
-    _check(lib().ds_bilateral_u16(ctx_for(_dev_index(depth_u16)), depth_u16.data_ptr(), n, h, w, d // 2, tabs[0].data_ptr(),
-                                  tabs[1].data_ptr(), 1 if wrap else 0, out.data_ptr(), _stream(depth_u16)))
-    return out
-
-
-# ---- depth refinement (csrc/ds_joint_bilateral.hip; public interface: src/depth_refine.py) ------------------------------------------
-_DEPTH_REFINE_TABLES = collections.OrderedDict()       # (device index, d, sigma_color, sigma_space) -> (ws, wc) on that device
-_DEPTH_REFINE_TABLES_MAX = 4
-_DEPTH_REFINE_LOCK = threading.Lock()
-DEPTH_REFINE_MAX_ITERATIONS = 8
+    return _filter_params("bilateral", "(d, sigma_color, sigma_space)", bilateral, "d", 3, 31, True, ("sigma_color", "sigma_space"))
 
 
 def depth_refine_params(p):
     """(d, sigma_color, sigma_space) or (d, sigma_color, sigma_space, iterations) as (int, float, float, int), or ValueError: d odd in
     3..31, both sigmas finite and > 0, iterations an integer in 1..8 (default 1); a bool is no integer.  Pure Python (the funnel
     checks its option with it before any device work)."""
-    try:
-        if isinstance(p, (str, bytes)) or len(p) not in (3, 4):
-            raise TypeError
-        d, sigma_color, sigma_space = p[0], p[1], p[2]
-        it = p[3] if len(p) == 4 else 1
-        ok_d = not isinstance(d, bool) and int(d) == d
-        ok_it = not isinstance(it, bool) and int(it) == it
-        d, sigma_color, sigma_space, it = int(d), float(sigma_color), float(sigma_space), int(it)
-    except (TypeError, ValueError, OverflowError, KeyError, IndexError):
-        raise ValueError("depth_refine must be (d, sigma_color, sigma_space) or (d, sigma_color, sigma_space, iterations), got %r" % (p,)) from None
-    if not (ok_d and d % 2 == 1 and 3 <= d <= 31):
-        raise ValueError("depth_refine: d must be an odd integer in 3..31, got %r" % (p[0],))
-    if not (0.0 < sigma_color < math.inf and 0.0 < sigma_space < math.inf):
-        raise ValueError("depth_refine: sigma_color and sigma_space must be finite and > 0, got %r, %r" % (sigma_color, sigma_space))
-    if not (ok_it and 1 <= it <= DEPTH_REFINE_MAX_ITERATIONS):
-        raise ValueError("depth_refine: iterations must be an integer in 1..%d, got %r" % (DEPTH_REFINE_MAX_ITERATIONS, p[3] if len(p) == 4 else it))
-    return d, sigma_color, sigma_space, it
+    return _filter_params("depth_refine", "(d, sigma_color, sigma_space) or (d, sigma_color, sigma_space, iterations)", p, "d", 3, 31, True,
+                          ("sigma_color", "sigma_space"), DEPTH_REFINE_MAX_ITERATIONS)
+
+
+def stabilize_params(params):
+    """(radius, sigma_color, sigma_time) as (int, float, float), or ValueError: radius an integer in 1..4 (a bool is no integer), both
+    sigmas finite and > 0.  Pure Python (gen_frames_sharded checks its option with it before any device work)."""
+    return _filter_params("stabilize", "(radius, sigma_color, sigma_time)", params, "radius", 1, STABILIZE_MAX_RADIUS, False,
+                          ("sigma_color", "sigma_time"))
+
+
+def spatial_weight_table(d, sigma_space):
+    """ws of ds_bilateral_u16 and ds_joint_bilateral_u16: d * d float64 in raster order, exp(-(dx^2 + dy^2) / (2 sigma_space^2)) inside
+    the circle of radius d // 2, exactly 0 outside."""
+    r = d // 2
+    dy, dx = np.mgrid[-r:r + 1, -r:r + 1]
+    return np.where(dx * dx + dy * dy <= r * r, np.exp(-(dx * dx + dy * dy) / (2.0 * sigma_space**2)), 0.0).astype(np.float64).ravel()
 
 
 def color_weight_table(sigma_color):
@@ -418,13 +417,75 @@ def color_weight_table(sigma_color):
     return np.exp(-(np.arange(766, dtype=np.float64)**2) / (2.0 * sigma_color**2))
 
 
+def bilateral_tables(d, sigma_color, sigma_space):
+    """The two host-made tables of ds_bilateral_u16 (include/depthstereo.h), float64: ws (spatial_weight_table) and wr (65536,
+    indexed by the integer |D(q) - D(p)|)."""
+    return spatial_weight_table(d, sigma_space), np.exp(-(np.arange(65536, dtype=np.float64)**2) / (2.0 * sigma_color**2))
+
+
 def depth_refine_tables(d, sigma_color, sigma_space):
-    """The two host-made tables of ds_joint_bilateral_u16 (include/depthstereo.h), float64: ws (d * d, raster order, exactly 0 outside
-    the circle of radius d // 2) and wc (766, indexed by the integer |dR| + |dG| + |dB| of two guide pixels)."""
-    r = d // 2
-    dy, dx = np.mgrid[-r:r + 1, -r:r + 1]
-    ws = np.where(dx * dx + dy * dy <= r * r, np.exp(-(dx * dx + dy * dy) / (2.0 * sigma_space**2)), 0.0).astype(np.float64).ravel()
-    return ws, color_weight_table(sigma_color)
+    """The two host-made tables of ds_joint_bilateral_u16 (include/depthstereo.h), float64: ws (spatial_weight_table) and wc
+    (color_weight_table)."""
+    return spatial_weight_table(d, sigma_space), color_weight_table(sigma_color)
+
+
+def temporal_joint_bilateral_tables(radius, sigma_color, sigma_time):
+    """The two host-made tables of ds_temporal_joint_bilateral_u16 (include/depthstereo.h), float64: wt (radius + 1,
+    wt[a] = exp(-a^2 / (2 sigma_time^2)), wt[0] == 1.0) and wc (color_weight_table: depth refinement's table)."""
+    wt = np.exp(-(np.arange(radius + 1, dtype=np.float64)**2) / (2.0 * sigma_time**2))
+    return wt, color_weight_table(sigma_color)
+
+
+def stabilize_tables_on(device, radius, sigma_color, sigma_time):
+    """(wt, wc) of temporal_joint_bilateral_tables as float64 tensors on `device`; on a GPU they are uploaded once and kept for the
+    last 4 (device, radius, sigma_color, sigma_time)."""
+    torch = _torch()
+    if torch.device(device).type != "cuda":
+        return tuple(torch.from_numpy(t) for t in temporal_joint_bilateral_tables(radius, sigma_color, sigma_time))
+    return _tables_on("stabilize", device, (radius, sigma_color, sigma_time), temporal_joint_bilateral_tables)
+
+
+def _check_depth_guide(name, depth_u16, guide_u8=None, contiguous=False):
+    """DepthStereoError unless depth is a uint16 cuda tensor [n,h,w] and -- where given -- guide a uint8 cuda tensor [n,h,w,3 or 4] on
+    the depth's device and of its size; contiguous: both must already be dense (a caller that may copy calls .contiguous() itself)."""
+    torch = _torch()
+    dense = "contiguous " if contiguous else ""
+    if not (torch.is_tensor(depth_u16) and depth_u16.is_cuda and depth_u16.dtype == torch.uint16 and depth_u16.dim() == 3
+            and (depth_u16.is_contiguous() or not contiguous)):
+        raise DepthStereoError("%s: depth must be a %suint16 cuda tensor [n,h,w], got %s %s"
+                               % (name, dense, getattr(depth_u16, "dtype", type(depth_u16)), tuple(getattr(depth_u16, "shape", ()))))
+    if guide_u8 is None:
+        return
+    if not (torch.is_tensor(guide_u8) and guide_u8.is_cuda and guide_u8.dtype == torch.uint8 and guide_u8.dim() == 4
+            and guide_u8.device == depth_u16.device and tuple(guide_u8.shape[:3]) == tuple(depth_u16.shape) and guide_u8.shape[3] in (3, 4)
+            and (guide_u8.is_contiguous() or not contiguous)):
+        raise DepthStereoError("%s: guide must be a %suint8 cuda tensor [n,h,w,3 or 4] on the depth's device and of its size %s, got %s %s"
+                               % (name, dense, tuple(depth_u16.shape), getattr(guide_u8, "dtype", type(guide_u8)),
+                                  tuple(getattr(guide_u8, "shape", ()))))
+
+
+def bilateral_u16(depth_u16, d, sigma_color, sigma_space, wrap=False):
+    """Bilateral filter of uint16 depth maps [n,h,w] (cuda) -> float64 [n,h,w] in the same units (ds_bilateral_u16: the definition is
+    in include/depthstereo.h).  d: odd window diameter 3..31; sigma_color in uint16 levels (the range table is indexed by an integer
+    difference); sigma_space in pixels; wrap: tap indices modulo the image size instead of BORDER_REFLECT_101 (which needs
+    d // 2 < min(h, w)).  The tables are made on the host, uploaded once and kept for the last 4 (device, d, sigma_color,
+    sigma_space)."""
+    torch = require_gpu()
+    try:
+        d, sigma_color, sigma_space = bilateral_params((d, sigma_color, sigma_space))
+    except ValueError as e:
+        raise DepthStereoError("bilateral_u16: %s" % e) from None
+    _check_depth_guide("bilateral_u16", depth_u16)
+    depth_u16 = depth_u16.contiguous()
+    n, h, w = depth_u16.shape
+    if not wrap and d // 2 >= min(h, w):
+        raise DepthStereoError("bilateral_u16: d // 2 = %d must be below min(h, w) = %d without wrap" % (d // 2, min(h, w)))
+    ws, wr = _tables_on("bilateral", depth_u16.device, (d, sigma_color, sigma_space), bilateral_tables)
+    out = torch.empty((n, h, w), dtype=torch.float64, device=depth_u16.device)
+    CALLS["ds_bilateral_u16"] += 1
+    _check(lib().ds_bilateral_u16(ctx_for(_dev_index(depth_u16)), depth_u16.data_ptr(), n, h, w, d // 2, ws.data_ptr(),
+                                  wr.data_ptr(), 1 if wrap else 0, out.data_ptr(), _stream(depth_u16)))
+    return out
 
 
 def joint_bilateral_u16(depth_u16, guide_u8, d, sigma_color, sigma_space, iterations=1, wrap=False):
@@ -439,39 +500,21 @@ def joint_bilateral_u16(depth_u16, guide_u8, d, sigma_color, sigma_space, iterat
         d, sigma_color, sigma_space, iterations = depth_refine_params((d, sigma_color, sigma_space, iterations))
     except ValueError as e:
         raise DepthStereoError("joint_bilateral_u16: %s" % e) from None
-    if not (torch.is_tensor(depth_u16) and depth_u16.is_cuda and depth_u16.dtype == torch.uint16 and depth_u16.dim() == 3):
-        raise DepthStereoError("joint_bilateral_u16: depth must be a uint16 cuda tensor [n,h,w], got %s %s"
-                               % (getattr(depth_u16, "dtype", type(depth_u16)), tuple(getattr(depth_u16, "shape", ()))))
-    if not (torch.is_tensor(guide_u8) and guide_u8.is_cuda and guide_u8.dtype == torch.uint8 and guide_u8.dim() == 4
-            and guide_u8.device == depth_u16.device and tuple(guide_u8.shape[:3]) == tuple(depth_u16.shape) and guide_u8.shape[3] in (3, 4)):
-        raise DepthStereoError("joint_bilateral_u16: guide must be a uint8 cuda tensor [n,h,w,3 or 4] on the depth's device and of its "
-                               "size %s, got %s %s" % (tuple(depth_u16.shape), getattr(guide_u8, "dtype", type(guide_u8)),
-                                                       tuple(getattr(guide_u8, "shape", ()))))
+    _check_depth_guide("joint_bilateral_u16", depth_u16, guide_u8)
     depth_u16, guide_u8 = depth_u16.contiguous(), guide_u8.contiguous()
     n, h, w = depth_u16.shape
     if n == 0 or h == 0 or w == 0:
         raise DepthStereoError("joint_bilateral_u16: empty depth %s" % (tuple(depth_u16.shape),))
     if not wrap and d // 2 >= min(h, w):
         raise DepthStereoError("joint_bilateral_u16: d // 2 = %d must be below min(h, w) = %d without wrap" % (d // 2, min(h, w)))
-    key = (_dev_index(depth_u16), d, sigma_color, sigma_space)
-    with _DEPTH_REFINE_LOCK:
-        tabs = _DEPTH_REFINE_TABLES.get(key)
-        if tabs is None:
-            ws, wc = depth_refine_tables(d, sigma_color, sigma_space)
-            tabs = _DEPTH_REFINE_TABLES[key] = (torch.from_numpy(ws).to(depth_u16.device), torch.from_numpy(wc).to(depth_u16.device))
-            while len(_DEPTH_REFINE_TABLES) > _DEPTH_REFINE_TABLES_MAX:
-                _DEPTH_REFINE_TABLES.popitem(last=False)
-        else:
-            _DEPTH_REFINE_TABLES.move_to_end(key)
-    for t in tabs:                   # an evicted table may still be read by a launch on this stream: tell the allocator
-        t.record_stream(torch.cuda.current_stream(depth_u16.device))
+    ws, wc = _tables_on("depth_refine", depth_u16.device, (d, sigma_color, sigma_space), depth_refine_tables)
     src = depth_u16
     bufs = [torch.empty((n, h, w), dtype=torch.uint16, device=depth_u16.device) for _ in range(min(iterations, 2))]
     for i in range(iterations):
         out = bufs[i & 1]
         CALLS["ds_joint_bilateral_u16"] += 1
         _check(lib().ds_joint_bilateral_u16(ctx_for(_dev_index(depth_u16)), src.data_ptr(), guide_u8.data_ptr(), guide_u8.shape[3], n, h, w,
-                                            d // 2, tabs[0].data_ptr(), tabs[1].data_ptr(), 1 if wrap else 0, out.data_ptr(),
+                                            d // 2, ws.data_ptr(), wc.data_ptr(), 1 if wrap else 0, out.data_ptr(),
                                             _stream(depth_u16)))
         src = out
     return src
@@ -521,76 +564,14 @@ def temporal_smooth5(src, first, count, lo, hi, out=None):
     return out
 
 
-# the temporal depth filter (ds_temporal_joint_bilateral_u16; public interface: video_mode.stabilize_depth)
-_STABILIZE_TABLES = collections.OrderedDict()          # (device index, radius, sigma_color, sigma_time) -> (wt, wc) on that device
-_STABILIZE_TABLES_MAX = 4
-_STABILIZE_LOCK = threading.Lock()
-STABILIZE_MAX_RADIUS = 4
-
-
-def stabilize_params(params):
-    """(radius, sigma_color, sigma_time) as (int, float, float), or ValueError: radius an integer in 1..4 (a bool is no integer), both
-    sigmas finite and > 0.  Pure Python (gen_frames_sharded checks its option with it before any device work)."""
-    try:
-        if isinstance(params, (str, bytes)) or len(params) != 3:
-            raise TypeError
-        radius, sigma_color, sigma_time = params[0], params[1], params[2]
-        ok_r = not isinstance(radius, (bool, np.bool_)) and int(radius) == radius
-        radius, sigma_color, sigma_time = int(radius), float(sigma_color), float(sigma_time)
-    except (TypeError, ValueError, OverflowError, KeyError, IndexError):
-        raise ValueError("stabilize must be (radius, sigma_color, sigma_time), got %r" % (params,)) from None
-    if not (ok_r and 1 <= radius <= STABILIZE_MAX_RADIUS):
-        raise ValueError("stabilize: radius must be an integer in 1..%d, got %r" % (STABILIZE_MAX_RADIUS, params[0]))
-    if not (0.0 < sigma_color < math.inf and 0.0 < sigma_time < math.inf):
-        raise ValueError("stabilize: sigma_color and sigma_time must be finite and > 0, got %r, %r" % (sigma_color, sigma_time))
-    return radius, sigma_color, sigma_time
-
-
-def temporal_joint_bilateral_tables(radius, sigma_color, sigma_time):
-    """The two host-made tables of ds_temporal_joint_bilateral_u16 (include/depthstereo.h), float64: wt (radius + 1,
-    wt[a] = exp(-a^2 / (2 sigma_time^2)), wt[0] == 1.0) and wc (766: depth refinement's table, from the same code)."""
-    wt = np.exp(-(np.arange(radius + 1, dtype=np.float64)**2) / (2.0 * sigma_time**2))
-    return wt, color_weight_table(sigma_color)
-
-
-def stabilize_tables_on(device, radius, sigma_color, sigma_time):
-    """(wt, wc) of temporal_joint_bilateral_tables as float64 tensors on `device`; on a GPU they are uploaded once and kept for the
-    last 4 (device, radius, sigma_color, sigma_time)."""
-    torch = _torch()
-    device = torch.device(device)
-    if device.type != "cuda":
-        return tuple(torch.from_numpy(t) for t in temporal_joint_bilateral_tables(radius, sigma_color, sigma_time))
-    key = (device.index if device.index is not None else torch.cuda.current_device(), radius, sigma_color, sigma_time)
-    with _STABILIZE_LOCK:
-        tabs = _STABILIZE_TABLES.get(key)
-        if tabs is None:
-            tabs = _STABILIZE_TABLES[key] = tuple(torch.from_numpy(t).to(device)
-                                                  for t in temporal_joint_bilateral_tables(radius, sigma_color, sigma_time))
-            while len(_STABILIZE_TABLES) > _STABILIZE_TABLES_MAX:
-                _STABILIZE_TABLES.popitem(last=False)
-        else:
-            _STABILIZE_TABLES.move_to_end(key)
-    for t in tabs:                       # an evicted table may still be read by a launch on this stream: tell the allocator
-        t.record_stream(torch.cuda.current_stream(device))
-    return tabs
-
-
+# the temporal depth filter (its tables and parameters: the bilateral family, above; public interface: video_mode.stabilize_depth)
 def temporal_joint_bilateral_u16(depth_u16, guide_u8, radius, wt, wc, first, count, lo, hi, out=None):
     """The temporal joint bilateral filter (ds_temporal_joint_bilateral_u16, include/depthstereo.h): depth uint16 cuda [m,h,w] contiguous,
     guide uint8 cuda [m,h,w,3 or 4] contiguous (any byte alignment) -> uint16 [count,h,w], frames first .. first + count - 1 filtered over
     the frames within `radius` of each that lie in lo..hi.  wt, wc: float64 cuda tensors of radius + 1 and 766 values
     (stabilize_tables_on).  out: write into this contiguous uint16 tensor of that shape (it must not overlap depth)."""
     torch = require_gpu()
-    if not (torch.is_tensor(depth_u16) and depth_u16.is_cuda and depth_u16.dtype == torch.uint16 and depth_u16.dim() == 3
-            and depth_u16.is_contiguous()):
-        raise DepthStereoError("temporal_joint_bilateral_u16: depth must be a contiguous uint16 cuda tensor [m,h,w], got %s %s"
-                               % (getattr(depth_u16, "dtype", type(depth_u16)), tuple(getattr(depth_u16, "shape", ()))))
-    if not (torch.is_tensor(guide_u8) and guide_u8.is_cuda and guide_u8.dtype == torch.uint8 and guide_u8.dim() == 4
-            and guide_u8.device == depth_u16.device and tuple(guide_u8.shape[:3]) == tuple(depth_u16.shape) and guide_u8.shape[3] in (3, 4)
-            and guide_u8.is_contiguous()):
-        raise DepthStereoError("temporal_joint_bilateral_u16: guide must be a contiguous uint8 cuda tensor [m,h,w,3 or 4] on the depth's "
-                               "device and of its size %s, got %s %s" % (tuple(depth_u16.shape), getattr(guide_u8, "dtype", type(guide_u8)),
-                                                                         tuple(getattr(guide_u8, "shape", ()))))
+    _check_depth_guide("temporal_joint_bilateral_u16", depth_u16, guide_u8, contiguous=True)
     radius = int(radius)
     for name, t, n in (("wt", wt, radius + 1), ("wc", wc, 766)):
         if not (torch.is_tensor(t) and t.is_cuda and t.device == depth_u16.device and t.dtype == torch.float64 and t.dim() == 1
@@ -635,7 +616,6 @@ def convert_to_i16(arr):
 # ---- custom-depth ingest (csrc/ds_resample.hip; host half: src/resample_model.py) -------------------------------------------------
 CD_WIDEN, CD_SINGLE_BAND, CD_MULTI_BAND = 0, 1, 2
 _CD_WORKSPACE_BLOCKS = 256                       # DS_CD_WORKSPACE_BLOCKS
-_coeff_cache = collections.OrderedDict()         # (device, fixed point?, in, out) -> (bounds, tap-major weights, taps) on the device
 
 
 def _pixel_plane(src):
@@ -651,22 +631,18 @@ def _pixel_plane(src):
     return pix, n, h, w, c, w * c, h * w * c
 
 
-def _lanczos_coeffs_on(device, fixed_point, in_size, out_size):
-    torch = _torch()
+def _lanczos_tables(fixed_point, in_size, out_size):
     from . import resample_model as rm
-    key = (str(device), bool(fixed_point), int(in_size), int(out_size))
-    hit = _coeff_cache.get(key)
-    if hit is None:
-        taps, bounds, kk = rm.lanczos_coeffs(int(in_size), int(out_size))
-        if fixed_point:
-            kk = rm.fixed_point_coeffs(kk)
-        hit = (torch.from_numpy(np.array(bounds)).to(device), torch.from_numpy(np.array(kk.T, order='C')).to(device), taps)
-        _coeff_cache[key] = hit
-        while len(_coeff_cache) > 32:
-            _coeff_cache.popitem(last=False)
-    else:
-        _coeff_cache.move_to_end(key)
-    return hit
+    _, bounds, kk = rm.lanczos_coeffs(in_size, out_size)
+    if fixed_point:
+        kk = rm.fixed_point_coeffs(kk)
+    return np.array(bounds), np.array(kk.T, order='C')
+
+
+def _lanczos_coeffs_on(device, fixed_point, in_size, out_size):
+    """(bounds, tap-major weights, taps) of one axis on the device, kept for the last 32 (device, fixed point?, in, out)."""
+    bounds, weights = _tables_on("lanczos", device, (bool(fixed_point), int(in_size), int(out_size)), _lanczos_tables, keep=32)
+    return bounds, weights, weights.shape[0]
 
 
 def resize_lanczos(src, out_hw):

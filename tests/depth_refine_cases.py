@@ -3,8 +3,12 @@ bilateral filter of a uint16 depth map guided by an RGB image; the definition is
 the seeded inputs both files use.  The model is a loop over the taps in raster order, vectorised over the image: per pixel it performs
 the operations of the definition in the definition's order (one rounded multiply for the weight, the product rounded and then the sum
 rounded, one IEEE division, np.rint), so the kernel must reproduce it bit for bit.  It is written from the definition alone and shares
-no code with the product's table builder."""
+no code with the product's table builder -- nor with the unguided sibling's model in normalmap_bilateral_cases.py, although the two
+kernels are one routine now: a model that shared the product's structure could share its mistakes.  Only the depth inputs are shared."""
 import numpy as np
+
+# the depth inputs are those of the unguided sibling's tests, under the names the tests of depth refinement use
+from normalmap_bilateral_cases import CLIFF, STEP, cases as depth_cases, ramp_noise, random_depth, staircase  # noqa: F401
 
 
 def tables(d, sigma_color, sigma_space):
@@ -49,39 +53,6 @@ def model(depth, guide, params, wrap=False):
             num = num + wgt * pad[dy:dy + h, dx:dx + w]
             den = den + wgt
     return np.rint(num / den).astype(np.uint16)
-
-
-# ---- depth inputs (as in normalmap_bilateral_cases.py) ------------------------------------------------------------------------------
-def random_depth(h, w, seed, n=None):
-    """Full-range white noise: every neighbour matters, every index mistake shows."""
-    rng = np.random.default_rng(seed)
-    return rng.integers(0, 65536, ((h, w) if n is None else (n, h, w)), dtype=np.uint16)
-
-
-def ramp_noise(h, w, seed, n=None):
-    """A smooth ramp plus +-3 levels of noise."""
-    rng = np.random.default_rng(seed)
-    shape = (h, w) if n is None else (n, h, w)
-    y, x = np.mgrid[0:h, 0:w]
-    base = 20000 + 11 * x + 7 * y
-    return (base + rng.integers(-3, 4, shape)).astype(np.uint16)
-
-
-STEP = 6            # staircase: one-level steps, 6 pixels wide
-CLIFF = 4096
-
-
-def staircase(h, w, n=None, cliff_at=None):
-    """One-level steps STEP pixels wide along x, with one CLIFF-level cliff at column cliff_at (default: the middle)."""
-    cliff_at = w // 2 if cliff_at is None else cliff_at
-    x = np.arange(w)
-    row = 30000 + x // STEP + np.where(x >= cliff_at, CLIFF, 0)
-    img = np.broadcast_to(row, (h, w)).astype(np.uint16)
-    return img.copy() if n is None else np.stack([img] * n)
-
-
-def depth_cases(h, w, seed, n=None):
-    return [("random", random_depth(h, w, seed, n)), ("ramp", ramp_noise(h, w, seed + 1, n)), ("staircase", staircase(h, w, n))]
 
 
 # ---- guide inputs ---------------------------------------------------------------------------------------------------------------------

@@ -151,10 +151,52 @@ def test_table_cache_is_bounded(gpu):
     first = _filter(torch, d, g, (3, 10.0, 1.0))
     for k in range(6):
         _filter(torch, d, g, (3, 11.0 + k, 1.0))
-    assert len(_native._DEPTH_REFINE_TABLES) == 4
+    assert _native.cached_tables("depth_refine") == 4
     assert torch.equal(_filter(torch, d, g, (3, 10.0, 1.0)), first)                    # evicted and rebuilt: same bits
-    assert len(_native._DEPTH_REFINE_TABLES) == 4
+    assert _native.cached_tables("depth_refine") == 4
     assert np.array_equal(first.cpu().numpy(), rc.model(d, g, (3, 10.0, 1.0)))
+
+
+def test_families_share_one_cache_but_no_table(gpu):
+    """The tables of the pre-filter, of depth refinement and of the temporal filter live in ONE cache.  The same (3, 10.0, 1.0) names a
+    65536-entry wr, a 766-entry wc and a 4-entry wt: each family must get its own, and a family that overflows its bound of 4 must
+    evict only its own."""
+    torch = gpu
+    import normalmap_bilateral_cases as bc
+    import video_stabilize_cases as sc
+    from src import _native
+    P = (3, 10.0, 1.0)
+    d, g = rc.ramp_noise(8, 8, seed=1, n=1), rc.regions_guide(8, 8, seed=2, n=1)
+    x = torch.from_numpy(d).cuda()
+    want_plain, want_joint, (want_wt, want_wc) = bc.model(d, P), rc.model(d, g, P), sc.tables(*P)
+
+    def stabilize_tables():
+        wt, wc = _native.stabilize_tables_on(x.device, *P)
+        assert wt.is_cuda and wc.is_cuda and tuple(wt.shape) == (4,) and tuple(wc.shape) == (766,)
+        assert np.array_equal(wt.cpu().numpy(), want_wt) and np.array_equal(wc.cpu().numpy(), want_wc)
+
+    assert np.array_equal(_native.bilateral_u16(x, *P).cpu().numpy(), want_plain)
+    stabilize_tables()
+    assert np.array_equal(_filter(torch, d, g, P).cpu().numpy(), want_joint)
+    stabilize_tables()
+    assert np.array_equal(_native.bilateral_u16(x, *P).cpu().numpy(), want_plain)
+    families = ("bilateral", "depth_refine", "stabilize")
+    for family in families:
+        before = {f: _native.cached_tables(f) for f in families}
+        assert all(1 <= c <= 4 for c in before.values()), before
+        for k in range(5):                                                             # five further sets: past the bound whatever it held
+            if family == "bilateral":
+                _native.bilateral_u16(x, 3, 21.0 + k, 1.0)
+            elif family == "depth_refine":
+                _filter(torch, d, g, (3, 21.0 + k, 1.0))
+            else:
+                _native.stabilize_tables_on(x.device, 3, 21.0 + k, 1.0)
+        after = {f: _native.cached_tables(f) for f in families}
+        assert after == dict(before, **{family: 4}), (family, before, after)
+    # the three tables of P were evicted by their own families only, and come back with the same bits
+    assert np.array_equal(_native.bilateral_u16(x, *P).cpu().numpy(), want_plain)
+    assert np.array_equal(_filter(torch, d, g, P).cpu().numpy(), want_joint)
+    stabilize_tables()
 
 
 def test_entry_point_checks_its_arguments_without_a_launch(gpu):

@@ -168,9 +168,9 @@ def test_table_cache_is_bounded(gpu):
     first = _filter(torch, d, (3, 10.0, 1.0))
     for k in range(6):
         _filter(torch, d, (3, 11.0 + k, 1.0))
-    assert len(_native._BILATERAL_TABLES) == 4
+    assert _native.cached_tables("bilateral") == 4
     assert torch.equal(_filter(torch, d, (3, 10.0, 1.0)), first)                       # evicted and rebuilt: same bits
-    assert len(_native._BILATERAL_TABLES) == 4
+    assert _native.cached_tables("bilateral") == 4
 
 
 def test_entry_point_checks_its_arguments_without_a_launch(gpu):
