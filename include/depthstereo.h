@@ -113,6 +113,7 @@ int ds_profile_last_ms(ds_ctx *ctx, float *render_ms, float *exact_ms);
 #define DS_KT_LINEAR_SHUFFLE   7   /* ds_linear_shuffle */
 #define DS_KT_NORMALMAP        8   /* ds_normalmap (uint16, the fused kernel) */
 #define DS_KT_DEPTH_REFINE     9   /* ds_joint_bilateral_u16 */
+#define DS_KT_SPARSE_BILATERAL 10  /* ds_sparse_bilateral_f32, ds_sparse_bilateral_jump_f32 */
 #define DS_KT_RAGGED          12   /* + kind: the ragged round (k_linear_ragged) of that GEMM kind */
 int ds_kernel_timer_enable(ds_ctx *ctx, int enable);
 int ds_kernel_timer_read(ds_ctx *ctx, int kind, int64_t *launches, double *total_ms);
@@ -267,6 +268,44 @@ int ds_bilateral_u16(ds_ctx *ctx, const uint16_t *depth, int n, int h, int w, in
  */
 int ds_joint_bilateral_u16(ds_ctx *ctx, const uint16_t *depth, const uint8_t *guide, int guide_channels, int n, int h, int w, int radius,
                            const double *ws, const double *wc, int wrap, uint16_t *out, void *stream);
+
+/*
+ * ds_sparse_bilateral_f32 -- one pass of the 3D-photo pipeline's depth preparation: the discontinuity-masked median that
+ * inpaint.bilateral_filtering.sparse_bilateral_filtering runs (five times by default) on the float32 depth map in front of the mesh
+ * code.  The reference is a Python loop over every pixel (inpaint/bilateral_filtering.py:105-172, the branch with a discontinuity
+ * map and no mask; sigma_s and sigma_r are read there and never used).  A pass computes no depth: every output is ONE OF THE WINDOW'S
+ * DEPTHS, so the result equals the reference bit for bit.  This comment is the definition.
+ * V [n,h,w] float32: the map of this pass.  V0 [n,h,w] float32: the map the driver was called with (V0 == V as one buffer is legal:
+ * the first pass).  window s: odd, 1..15, m = s / 2.  t = threshold.  c(i, size) = min(max(i, 1), size - 2).
+ *   disp = 1.0f / V, one correctly rounded binary32 division (1 / 0 = inf).
+ *   Jump map J of V: for 1 <= y <= h - 2 and 1 <= x <= w - 2, J(y, x) = 1 if |disp(y, x) - disp(q)| > t in binary32 for any of the
+ *       four neighbours q (up, down, left, right), else 0; J = 0 on the outermost ring.  IEEE throughout: inf - finite is a jump,
+ *       inf - inf is NaN and NaN is no jump.
+ *   Discontinuity map D = J | (V0 == 0): V0, the ORIGINAL map, on every pass.
+ *   The tap at window offset (dy, dx), -m <= dy, dx <= m, of pixel (y, x) reads V and D at (c(y + dy, h), c(x + dx, w)): the
+ *       outermost ring is replaced by its inner neighbour, and the same clamp pads the image by any width.
+ *   out(y, x): if no tap has D set, the centre tap.  Else, with n the number of taps with D == 0: the centre tap if n == 0, else the
+ *       tap value of 0-based rank rank[n] in ascending order among those n taps (ties carry equal values: their order is immaterial).
+ *   rank: 226 int32 made on the host (src/_native.py: sparse_bilateral_rank_table), rank[n] = np.digitize(0.5, np.cumsum(c / c.sum()))
+ *       with c = np.ones(n, np.float32): the reference's float32 running sum of 1 / n.  It is NOT n / 2 (n = 20, 22, 28, 36, 40, 44,
+ *       48 ... differ); no kernel holds a closed form of it.
+ *   jump [n,h,w] uint8 receives J (not D): the driver blackens its image of the pass with it.
+ * Precondition: every V and V0 finite and >= 0 (the order of such binary32 values is the order of their bit patterns, which is what
+ * the selection compares).  Other values are memory-safe and give J by the rules above, but out is unspecified.
+ * A pixel's bits depend on its window alone: not on the tiling of the launch, the batch size or its position in the batch; the NumPy
+ * model is tests/sparse_bilateral_cases.py.
+ * DS_EINVAL: a null pointer; n <= 0; h < 3 or w < 3 (the reference fails there); window even or outside 1..15; V, V0, out or rank
+ * not 4-byte aligned; out overlapping V or V0; jump overlapping V, V0 or out.  DS_EUNSUPPORTED: n > 65535 or h > 32 * 65535 (the limits of ds_bilateral_u16), or an image of
+ * more than 2^31 - 1 tiles of 64 x 8 pixels.  Every
+ * refusal returns before any launch.  Asynchronous on `stream`; one kernel, no workspace; the kernel timer DS_KT_SPARSE_BILATERAL
+ * brackets the launch.
+ *
+ * ds_sparse_bilateral_jump_f32 -- J of V alone, by the same rules and with the same checks (those that name its arguments) and
+ * timer: the image of the driver's LAST pass needs the jump map of that pass's input, and nothing returns that pass's output.
+ */
+int ds_sparse_bilateral_f32(ds_ctx *ctx, const float *v, const float *v0, int n, int h, int w, int window, float threshold,
+                            const int32_t *rank, float *out, uint8_t *jump, void *stream);
+int ds_sparse_bilateral_jump_f32(ds_ctx *ctx, const float *v, int n, int h, int w, float threshold, uint8_t *jump, void *stream);
 
 /*
  * ds_frame_luma_hist -- per-frame luma histograms of a uint8 clip: the input of video mode's scene-cut detector (the reference

@@ -27,7 +27,7 @@ EXPORTS = [
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
-    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
+    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
     "ds_preprocess_bicubic_rows", "ds_tokens_fixup", "ds_upsample_bicubic_to_f32", "ds_im2col3x3_s2_nhwc", "ds_dpt_head_front",
 ]
 
@@ -87,6 +87,8 @@ def lib():
                 getattr(L, name + "_wrap").argtypes = getattr(L, name).argtypes
             L.ds_bilateral_u16.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, ci, vp, vp]
             L.ds_joint_bilateral_u16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp]
+            L.ds_sparse_bilateral_f32.argtypes = [vp, vp, vp, ci, ci, ci, ci, ctypes.c_float, vp, vp, vp, vp]
+            L.ds_sparse_bilateral_jump_f32.argtypes = [vp, vp, ci, ci, ci, ctypes.c_float, vp, vp]
             L.ds_frame_luma_hist.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_smooth5_f32.argtypes = [vp, vp, ci, i64, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_joint_bilateral_u16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp]
@@ -346,7 +348,8 @@ def _tables_on(family, device, params, build, keep=4):
 
 
 def cached_tables(family):
-    """How many (device, params) the table cache holds for `family`: "bilateral", "depth_refine", "stabilize" or "lanczos"."""
+    """How many (device, params) the table cache holds for `family`: "bilateral", "depth_refine", "sparse_bilateral", "stabilize" or
+    "lanczos"."""
     with _TABLES_LOCK:
         return len(_TABLES[family])
 
@@ -518,6 +521,107 @@ def joint_bilateral_u16(depth_u16, guide_u8, d, sigma_color, sigma_space, iterat
                                             _stream(depth_u16)))
         src = out
     return src
+
+
+# ---- the 3D-photo depth preparation (csrc/ds_sparse_bilateral.hip; public interface: inpaint/bilateral_filtering.py) ----------------
+SPARSE_BILATERAL_MAX_WINDOW = 15
+
+
+def sparse_bilateral_rank_table(nmax=225):
+    """rank of ds_sparse_bilateral_f32 (include/depthstereo.h): nmax + 1 int32, rank[n] = which of n equally weighted taps, in ascending
+    order, the reference's weighted median picks.  These are the reference's own NumPy calls on n float32 ones -- a float32 running sum
+    of 1 / n cut at 0.5 -- and NOT n // 2; no closed form is used anywhere."""
+    rank = np.zeros(nmax + 1, np.int32)
+    for n in range(1, nmax + 1):
+        c = np.ones(n, np.float32)
+        rank[n] = np.digitize(0.5, np.cumsum(c / c.sum()))
+    return rank
+
+
+def _sparse_bilateral_tables(nmax):
+    return (sparse_bilateral_rank_table(nmax),)
+
+
+def sparse_bilateral_windows(window_sizes):
+    """window_sizes as a list of ints, or ValueError: at least one, each an odd integer in 1..15 (a bool is no integer).  Pure Python."""
+    try:
+        if isinstance(window_sizes, (str, bytes)):
+            raise TypeError
+        got = [_as_int(s) for s in window_sizes]
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("window sizes must be a sequence of integers, got %r" % (window_sizes,)) from None
+    if not got:
+        raise ValueError("window sizes: at least one pass is needed")
+    for (s, ok), given in zip(got, window_sizes):
+        if not (ok and 1 <= s <= SPARSE_BILATERAL_MAX_WINDOW and s % 2 == 1):
+            raise ValueError("window size must be an odd integer in 1..%d, got %r" % (SPARSE_BILATERAL_MAX_WINDOW, given))
+    return [s for s, _ in got]
+
+
+def _check_sparse_map(name, depth_f32):
+    torch = _torch()
+    if not (torch.is_tensor(depth_f32) and depth_f32.is_cuda and depth_f32.dtype == torch.float32 and depth_f32.dim() == 3
+            and depth_f32.is_contiguous()):
+        raise DepthStereoError("%s: depth must be a contiguous float32 cuda tensor [n,h,w], got %s %s"
+                               % (name, getattr(depth_f32, "dtype", type(depth_f32)), tuple(getattr(depth_f32, "shape", ()))))
+    n, h, w = depth_f32.shape
+    if n < 1 or h < 3 or w < 3:
+        raise DepthStereoError("%s: needs n >= 1 and h, w >= 3, got %s" % (name, tuple(depth_f32.shape)))
+    return n, h, w
+
+
+def sparse_bilateral_pass_f32(v, v0, window, threshold):
+    """One pass (ds_sparse_bilateral_f32, include/depthstereo.h): v, v0 contiguous float32 cuda [n,h,w] (v0 the map of the first pass;
+    v0 is v is legal) -> (the filtered map float32 [n,h,w], the jump map of v uint8 [n,h,w])."""
+    torch = require_gpu()
+    n, h, w = _check_sparse_map("sparse_bilateral_pass_f32", v)
+    if v0 is not v:
+        if _check_sparse_map("sparse_bilateral_pass_f32", v0) != (n, h, w) or v0.device != v.device:
+            raise DepthStereoError("sparse_bilateral_pass_f32: v0 must have v's shape %s and device" % ((n, h, w),))
+    try:
+        window, = sparse_bilateral_windows([window])
+    except ValueError as e:
+        raise DepthStereoError("sparse_bilateral_pass_f32: %s" % e) from None
+    rank, = _tables_on("sparse_bilateral", v.device, (SPARSE_BILATERAL_MAX_WINDOW**2,), _sparse_bilateral_tables, keep=1)
+    out = torch.empty((n, h, w), dtype=torch.float32, device=v.device)
+    jump = torch.empty((n, h, w), dtype=torch.uint8, device=v.device)
+    CALLS["ds_sparse_bilateral_f32"] += 1
+    _check(lib().ds_sparse_bilateral_f32(ctx_for(_dev_index(v)), v.data_ptr(), v0.data_ptr(), n, h, w, window, float(threshold),
+                                         rank.data_ptr(), out.data_ptr(), jump.data_ptr(), _stream(v)))
+    return out, jump
+
+
+def sparse_bilateral_jump_f32(v, threshold):
+    """The jump map alone (ds_sparse_bilateral_jump_f32): v contiguous float32 cuda [n,h,w] -> uint8 [n,h,w]."""
+    torch = require_gpu()
+    n, h, w = _check_sparse_map("sparse_bilateral_jump_f32", v)
+    jump = torch.empty((n, h, w), dtype=torch.uint8, device=v.device)
+    CALLS["ds_sparse_bilateral_jump_f32"] += 1
+    _check(lib().ds_sparse_bilateral_jump_f32(ctx_for(_dev_index(v)), v.data_ptr(), n, h, w, float(threshold), jump.data_ptr(), _stream(v)))
+    return jump
+
+
+def sparse_bilateral_f32(depth_f32, window_sizes, threshold):
+    """The passes of sparse_bilateral_filtering on float32 depth maps [n,h,w] (cuda, contiguous): pass i has the odd window
+    window_sizes[i] in 1..15 and filters the result of pass i - 1 (the first one: depth_f32).  Returns (maps, jumps), two lists of
+    len(window_sizes) device tensors: maps[i] float32, the INPUT of pass i (maps[0] is depth_f32 itself), and jumps[i] uint8, the jump
+    map of maps[i] at `threshold` (float32).  One filter launch per pass except the last, whose output nothing asks for: that pass
+    makes its jump map alone.  Precondition: every value finite and >= 0 (include/depthstereo.h; the caller checks -- a device-side
+    test would cost a synchronisation)."""
+    require_gpu()
+    _check_sparse_map("sparse_bilateral_f32", depth_f32)
+    try:
+        windows = sparse_bilateral_windows(window_sizes)
+        threshold = float(threshold)
+    except (TypeError, ValueError) as e:
+        raise DepthStereoError("sparse_bilateral_f32: %s" % e) from None
+    maps, jumps = [depth_f32], []
+    for window in windows[:-1]:
+        out, jump = sparse_bilateral_pass_f32(maps[-1], depth_f32, window, threshold)
+        maps.append(out)
+        jumps.append(jump)
+    jumps.append(sparse_bilateral_jump_f32(maps[-1], threshold))
+    return maps, jumps
 
 
 # ---- video mode (csrc/ds_video.hip; host half: src/video_mode.py) ------------------------------------------------------------------
@@ -1106,7 +1210,7 @@ def dwconv(x, w_taps, bias_in, bias, kernel, stride, pad_top, pad_left, out_hw):
 
 
 KT_KINDS = {"linear_gelu": 0, "attention": 1, "linear_residual": 2, "linear": 3, "linear_vt": 4, "conv3x3": 5, "linear_readout": 6,
-            "linear_shuffle": 7, "normalmap": 8, "depth_refine": 9}
+            "linear_shuffle": 7, "normalmap": 8, "depth_refine": 9, "sparse_bilateral": 10}
 KT_RAGGED = 12
 
 
