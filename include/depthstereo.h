@@ -114,6 +114,7 @@ int ds_profile_last_ms(ds_ctx *ctx, float *render_ms, float *exact_ms);
 #define DS_KT_NORMALMAP        8   /* ds_normalmap (uint16, the fused kernel) */
 #define DS_KT_DEPTH_REFINE     9   /* ds_joint_bilateral_u16 */
 #define DS_KT_SPARSE_BILATERAL 10  /* ds_sparse_bilateral_f32, ds_sparse_bilateral_jump_f32 */
+#define DS_KT_AOMAP           11   /* ds_aomap_u16 */
 #define DS_KT_RAGGED          12   /* + kind: the ragged round (k_linear_ragged) of that GEMM kind */
 int ds_kernel_timer_enable(ds_ctx *ctx, int enable);
 int ds_kernel_timer_read(ds_ctx *ctx, int kind, int64_t *launches, double *total_ms);
@@ -306,6 +307,41 @@ int ds_joint_bilateral_u16(ds_ctx *ctx, const uint16_t *depth, const uint8_t *gu
 int ds_sparse_bilateral_f32(ds_ctx *ctx, const float *v, const float *v0, int n, int h, int w, int window, float threshold,
                             const int32_t *rank, float *out, uint8_t *jump, void *stream);
 int ds_sparse_bilateral_jump_f32(ds_ctx *ctx, const float *v, int n, int h, int w, float threshold, uint8_t *jump, void *stream);
+
+/*
+ * ds_aomap_u16 -- ambient-occlusion map of a uint16 depth map taken as a height field: per pixel, the mean over K directions of the
+ * sine of the horizon's elevation above the horizontal, subtracted from 1.  The reference has no counterpart; this comment is the
+ * definition, and the only normative text.
+ * Inputs.  depth D [n,h,w] uint16, white = near = high.  H = D, or H = 65535 - D with invert != 0.  radius R: an integer in 1..32.
+ *   directions K: one of 4, 8, 16.  relief: the height in pixels that the full uint16 range stands for, finite and > 0; intensity:
+ *   finite and > 0.  The host computes z = relief / 65535.0 and c = intensity / K in float64 and passes both as doubles.
+ * Rays.  The directions are the 16-point rose, indexed o = k * 16 / K for k = 0..K-1; q = o / 4 is the quadrant and r = o % 4 the
+ *   position inside it.  For step s = 1..R let m = rint(s * (sqrt(2.0) - 1.0)) in float64 (no s <= 32 comes within 0.0147 of a tie).
+ *   The base offset (dx, dy) is (s, 0) for r = 0, (s, m) for r = 1, (s, s) for r = 2, (m, s) for r = 3, rotated q times by
+ *   (x, y) -> (-y, x); x runs along a row and y down the rows.  A tap is kept iff d2 = dx^2 + dy^2 <= R^2 (at R = 1 the diagonals are
+ *   empty); the taps of a ray are visited in increasing s.
+ *   taps: int32 (dx, dy) pairs, ray after ray; dir_start: K + 1 int32, ray k owns taps dir_start[k] .. dir_start[k + 1] - 1.  Both are
+ *   made on the host (src/_native.py: aomap_offsets); no kernel holds a closed form.  A table that is not the one above cannot make
+ *   the kernel read outside its arguments (offsets are clamped to -R..R, indices to 0..16 R), but the output is then unspecified.
+ * Horizon of ray k at pixel p.  Start with bn = 0, bd = 1.  A tap at q = p + (dx, dy) takes part if it lies inside the image: with
+ *   wrap == 0 taps outside the image are skipped, with wrap != 0 indices are taken modulo the size, by as many periods as needed.
+ *   Let D = H(q) - H(p).  If D > 0 and D^2 * bd > bn^2 * d2, the tap becomes the best: bn = D, bd = d2.  The compare is exact (both
+ *   sides are below 2^43: 64-bit integers, or exact float64 products) and strict, so the earlier tap wins a tie.
+ * Value.  a = (double)bn * z;  o_k = a / sqrt((double)bd + a * a), each multiply, add, sqrt and division rounded on its own (no
+ *   contraction);  S = ((o_0 + o_1) + ...) + o_{K-1}, summed in direction order from 0.0 (a ray with no rising tap gives +0.0);
+ *   v = 1.0 - S * c, the product rounded first, then the difference.
+ * Outputs.  out_f64 [n,h,w] float64: v, unclamped; the pointer may be NULL.  out_u8 [n,h,w] uint8: rint(255.0 * min(max(v, 0.0), 1.0)),
+ *   rounding half to even.
+ * A pixel's bits depend on its rays alone: not on its tile, its position in the batch or the launch; the NumPy model is
+ * tests/aomap_cases.py.
+ * This is the height-field form of horizon-based ambient occlusion; it ignores the surface's own tilt, so a ramp darkens uniformly.
+ * DS_EINVAL, before any launch: a null pointer other than out_f64; n, h or w <= 0; radius outside 1..32; directions not in {4, 8, 16};
+ * z or c not finite or <= 0; taps or dir_start not 4-byte aligned, out_f64 not 8-byte aligned, depth not 2-byte aligned (out_u8 may
+ * have any alignment); an output overlapping depth or the other output.  DS_EUNSUPPORTED: n > 65535 or h > 32 * 65535.  Asynchronous
+ * on `stream`; one kernel, no workspace; the kernel timer DS_KT_AOMAP brackets the launch.
+ */
+int ds_aomap_u16(ds_ctx *ctx, const uint16_t *depth, int n, int h, int w, int radius, int directions, const int32_t *taps,
+                 const int32_t *dir_start, double z, double c, int invert, int wrap, uint8_t *out_u8, double *out_f64, void *stream);
 
 /*
  * ds_frame_luma_hist -- per-frame luma histograms of a uint8 clip: the input of video mode's scene-cut detector (the reference

@@ -27,7 +27,7 @@ EXPORTS = [
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
-    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
+    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_aomap_u16", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
     "ds_preprocess_bicubic_rows", "ds_tokens_fixup", "ds_upsample_bicubic_to_f32", "ds_im2col3x3_s2_nhwc", "ds_dpt_head_front",
 ]
 
@@ -89,6 +89,7 @@ def lib():
             L.ds_joint_bilateral_u16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp]
             L.ds_sparse_bilateral_f32.argtypes = [vp, vp, vp, ci, ci, ci, ci, ctypes.c_float, vp, vp, vp, vp]
             L.ds_sparse_bilateral_jump_f32.argtypes = [vp, vp, ci, ci, ci, ctypes.c_float, vp, vp]
+            L.ds_aomap_u16.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, cd, cd, ci, ci, vp, vp, vp]
             L.ds_frame_luma_hist.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_smooth5_f32.argtypes = [vp, vp, ci, i64, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_joint_bilateral_u16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp]
@@ -348,8 +349,8 @@ def _tables_on(family, device, params, build, keep=4):
 
 
 def cached_tables(family):
-    """How many (device, params) the table cache holds for `family`: "bilateral", "depth_refine", "sparse_bilateral", "stabilize" or
-    "lanczos"."""
+    """How many (device, params) the table cache holds for `family`: "bilateral", "depth_refine", "sparse_bilateral", "aomap", "stabilize"
+    or "lanczos"."""
     with _TABLES_LOCK:
         return len(_TABLES[family])
 
@@ -622,6 +623,84 @@ def sparse_bilateral_f32(depth_f32, window_sizes, threshold):
         jumps.append(jump)
     jumps.append(sparse_bilateral_jump_f32(maps[-1], threshold))
     return maps, jumps
+
+
+# ---- ambient-occlusion maps (csrc/ds_aomap.hip; public interface: src/aomap_generation.py) ------------------------------------------
+AOMAP_MAX_RADIUS = 32
+AOMAP_DIRECTIONS = (4, 8, 16)
+
+
+def aomap_params(p):
+    """(radius, directions, relief) or (radius, directions, relief, intensity) as (int, int, float, float), or ValueError: radius an
+    integer in 1..32, directions one of 4, 8, 16 (a bool is no integer), relief and intensity finite and > 0 (intensity defaults to
+    1.0).  Pure Python (the funnel checks its option with it before any device work)."""
+    usage = "(radius, directions, relief) or (radius, directions, relief, intensity)"
+    try:
+        if isinstance(p, (str, bytes)):
+            raise TypeError
+        q = tuple(p)
+        if len(q) not in (3, 4):
+            raise TypeError
+        (radius, ok_r), (directions, ok_k), relief = _as_int(q[0]), _as_int(q[1]), float(q[2])
+        intensity = float(q[3]) if len(q) == 4 else 1.0
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("aomap must be %s, got %r" % (usage, p)) from None
+    if not (ok_r and 1 <= radius <= AOMAP_MAX_RADIUS):
+        raise ValueError("aomap: radius must be an integer in 1..%d, got %r" % (AOMAP_MAX_RADIUS, q[0]))
+    if not (ok_k and directions in AOMAP_DIRECTIONS):
+        raise ValueError("aomap: directions must be 4, 8 or 16, got %r" % (q[1],))
+    if not (0.0 < relief < math.inf and 0.0 < intensity < math.inf):
+        raise ValueError("aomap: relief and intensity must be finite and > 0, got %r, %r" % (relief, intensity))
+    return radius, directions, relief, intensity
+
+
+def aomap_offsets(radius, directions):
+    """The ray table of ds_aomap_u16 (include/depthstereo.h): (taps, dir_start), taps int32 [T, 2] of (dx, dy) ray after ray in
+    increasing step, dir_start int32 [directions + 1].  Ray k is point k * 16 / directions of the 16-point rose; its steps s = 1..radius
+    are (s, 0), (s, m), (s, s) or (m, s) with m = rint(s * (sqrt(2) - 1)), turned by quarter turns (x, y) -> (-y, x), and kept inside
+    the circle dx^2 + dy^2 <= radius^2."""
+    s = np.arange(1, radius + 1, dtype=np.int64)
+    m = np.rint(s * (np.sqrt(2.0) - 1.0)).astype(np.int64)
+    base = (np.stack([s, 0 * s], 1), np.stack([s, m], 1), np.stack([s, s], 1), np.stack([m, s], 1))
+    quarter = np.array([[0, 1], [-1, 0]], dtype=np.int64)               # row vector (x, y) @ quarter = (-y, x)
+    rays = []
+    for k in range(directions):
+        turns, pos = divmod(k * 16 // directions, 4)
+        ray = base[pos] @ np.linalg.matrix_power(quarter, turns)
+        rays.append(ray[(ray * ray).sum(1) <= radius * radius])
+    dir_start = np.concatenate([[0], np.cumsum([len(r) for r in rays])]).astype(np.int32)
+    return np.concatenate(rays).astype(np.int32).reshape(-1, 2), dir_start
+
+
+def aomap_u16(depth_u16, radius, directions, relief, intensity=1.0, invert=False, wrap=False, want_f64=False, out=None):
+    """Ambient-occlusion maps of uint16 depth maps [n,h,w] (cuda) taken as height fields -> uint8 [n,h,w], 255 = open sky
+    (ds_aomap_u16: the definition is in include/depthstereo.h).  radius 1..32 pixels; directions 4, 8 or 16; relief: the height in
+    pixels that the full uint16 range stands for; intensity scales the occlusion; invert: black is high; wrap: tap indices modulo
+    the image size instead of skipping taps outside the image.  want_f64: return (uint8 map, the unclamped float64 value) instead.
+    out: write the uint8 map into this contiguous uint8 cuda tensor [n,h,w].  The ray table is made on the host, uploaded once and
+    kept for the last 4 (device, radius, directions)."""
+    torch = require_gpu()
+    try:
+        radius, directions, relief, intensity = aomap_params((radius, directions, relief, intensity))
+    except ValueError as e:
+        raise DepthStereoError("aomap_u16: %s" % e) from None
+    _check_depth_guide("aomap_u16", depth_u16)
+    depth_u16 = depth_u16.contiguous()
+    n, h, w = depth_u16.shape
+    if n == 0 or h == 0 or w == 0:
+        raise DepthStereoError("aomap_u16: empty depth %s" % (tuple(depth_u16.shape),))
+    if out is None:
+        out = torch.empty((n, h, w), dtype=torch.uint8, device=depth_u16.device)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == depth_u16.device and tuple(out.shape) == (n, h, w)
+              and out.is_contiguous()):
+        raise DepthStereoError("aomap_u16: out must be a contiguous uint8 tensor %s on the depth's device" % ((n, h, w),))
+    taps, dir_start = _tables_on("aomap", depth_u16.device, (radius, directions), aomap_offsets)
+    out_f64 = torch.empty((n, h, w), dtype=torch.float64, device=depth_u16.device) if want_f64 else None
+    CALLS["ds_aomap_u16"] += 1
+    _check(lib().ds_aomap_u16(ctx_for(_dev_index(depth_u16)), depth_u16.data_ptr(), n, h, w, radius, directions, taps.data_ptr(),
+                              dir_start.data_ptr(), relief / 65535.0, intensity / directions, 1 if invert else 0, 1 if wrap else 0,
+                              out.data_ptr(), out_f64.data_ptr() if want_f64 else None, _stream(depth_u16)))
+    return (out, out_f64) if want_f64 else out
 
 
 # ---- video mode (csrc/ds_video.hip; host half: src/video_mode.py) ------------------------------------------------------------------
@@ -1210,7 +1289,7 @@ def dwconv(x, w_taps, bias_in, bias, kernel, stride, pad_top, pad_left, out_hw):
 
 
 KT_KINDS = {"linear_gelu": 0, "attention": 1, "linear_residual": 2, "linear": 3, "linear_vt": 4, "conv3x3": 5, "linear_readout": 6,
-            "linear_shuffle": 7, "normalmap": 8, "depth_refine": 9, "sparse_bilateral": 10}
+            "linear_shuffle": 7, "normalmap": 8, "depth_refine": 9, "sparse_bilateral": 10, "aomap": 11}
 KT_RAGGED = 12
 
 

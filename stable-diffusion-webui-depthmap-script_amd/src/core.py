@@ -439,7 +439,7 @@ def _mark(g, name, stream=None):
 
 
 def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=None, normalmap_wrap=False, normalmap_bilateral=None,
-                  depth_refine=None, depth_refine_wrap=False):
+                  depth_refine=None, depth_refine_wrap=False, aomap=None, aomap_wrap=False):
     """Enqueue everything a group needs on the current stream -- H2D, network, post-processing, stereo, normal map, heat
     map, D2H into pinned buffers -- and return the handles; nothing here waits for the device except the post-processing
     branches that must know which predictions are flat (one sync per batch) and the percentile bisection of 'Outliers'."""
@@ -621,6 +621,9 @@ def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=Non
         if inp[go.GEN_HEATMAP]:                                                                      # :271-274
             from .heatmap import colorize_batch
             download(colorize_batch(d16), "heatmap")
+        if aomap is not None:                                                                        # ops['aomap'] (src/aomap_generation.py)
+            from .aomap_generation import create_aomap_batch
+            download(create_aomap_batch(d16, *aomap, wrap=aomap_wrap), "aomap")
         _mark(g, "per-pixel kernels done")
         ready = torch.cuda.Event()
         ready.record()                                        # everything the copies read has been enqueued (main or post stream)
@@ -813,6 +816,8 @@ def _unit_tasks(g, j):
         tasks.append(("normalmap", lambda: ('normalmap', _to_pil(host["normalmap"].numpy()[j]))))
     if inp[go.GEN_HEATMAP]:
         tasks.append(("heatmap", lambda: ('heatmap', _to_pil(host["heatmap"].numpy()[j]))))
+    if "aomap" in host:                                  # ops['aomap'] of this call: after the reference's outputs, before the mesh
+        tasks.append(("aomap", lambda: ('aomap', _to_pil(host["aomap"].numpy()[j]))))
     return tasks
 
 
@@ -921,8 +926,23 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
             raise ValueError("ops['depth_refine_wrap'] must be True, False or 'tiling', got %r" % (depth_refine_wrap,))
         depth_refine_wrap = bool(inp[go.TILING_MODE])
     depth_refine_wrap = bool(depth_refine_wrap)
+    # ops['aomap'] (not in the reference): (radius, directions, relief[, intensity]) = an ambient-occlusion map of the uint16 depth map
+    # (src/aomap_generation.py), computed from the map the normal map reads -- behind depth_refine, the refined one -- and yielded as
+    # (i, 'aomap', image) after 'heatmap'; absent / None = off, and then the call makes the launches, uploads and bytes it always made.
+    # ops['aomap_wrap']: True, False or 'tiling' (exactly when TILING_MODE is on): rays continue on the other side of the map.  Options
+    # of THIS call, checked here before any device work.
+    aomap = ops.get('aomap')
+    if aomap is not None:
+        aomap = _native.aomap_params(aomap)
+    aomap_wrap = ops.get('aomap_wrap', False)
+    if isinstance(aomap_wrap, str):
+        if aomap_wrap != 'tiling':
+            raise ValueError("ops['aomap_wrap'] must be True, False or 'tiling', got %r" % (aomap_wrap,))
+        aomap_wrap = bool(inp[go.TILING_MODE])
+    aomap_wrap = bool(aomap_wrap)
     model_holder.update_settings(**{k: v for k, v in ops.items()
-                                    if k not in ('normalmap_wrap', 'normalmap_bilateral', 'depth_refine', 'depth_refine_wrap')})
+                                    if k not in ('normalmap_wrap', 'normalmap_bilateral', 'depth_refine', 'depth_refine_wrap', 'aomap',
+                                                 'aomap_wrap')})
 
     torch = _native.require_gpu()        # the hot path has no CPU implementation, whatever COMPUTE_DEVICE says
     device = torch.device('cuda', torch.cuda.current_device())
@@ -953,7 +973,7 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
             try:
                 _t0 = _time.perf_counter()
                 launched, failure = _launch_group(gi & 1, idxs, inputimages, inputdepthmaps, inp, device, stats, normalmap_wrap,
-                                                  normalmap_bilateral, depth_refine, depth_refine_wrap), None
+                                                  normalmap_bilateral, depth_refine, depth_refine_wrap, aomap, aomap_wrap), None
                 stats["launch"] = stats.get("launch", 0.0) + (_time.perf_counter() - _t0)
             except Exception as e:          # noqa: BLE001 -- re-raised below, after the results that precede it
                 launched, failure = None, e
