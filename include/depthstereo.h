@@ -344,6 +344,38 @@ int ds_aomap_u16(ds_ctx *ctx, const uint16_t *depth, int n, int h, int w, int ra
                  const int32_t *dir_start, double z, double c, int invert, int wrap, uint8_t *out_u8, double *out_f64, void *stream);
 
 /*
+ * ds_lensblur_u8 -- lens blur from depth: a synthetic shallow depth of field, gathered per output pixel over a disc whose radius
+ * follows the distance of the depth from a focus depth, with an occlusion rule.  The reference has no counterpart; this comment is the
+ * definition, and the only normative text.  Everything is an integer: every sum is order-independent.
+ * Inputs, per batch.  image [n,h,w,3] uint8.  depth [n,h,w] uint16.  focus [n] uint16, on the device: one focus depth per image, in the
+ *   units of depth as stored.  Integers R in 1..32 (the largest blur radius in pixels), A in 1..65535, band in 0..65535.  Flag invert.
+ * Nearness.  z = depth, or 65535 - depth with invert != 0; a larger z is nearer.
+ * Circle of confusion, in quarter pixels.  e = max(|depth - focus| - band, 0);  rho = min(4 R, (e * A + 32768) >> 16), where
+ *   e * A + 32768 < 2^32.  rho does not depend on invert.
+ * Disc and weights.  For rho in 0..4 R:  n(rho) = #{(dx, dy) in Z^2 : 16 (dx^2 + dy^2) <= rho^2}  and  W[rho] = 2^20 // n(rho).
+ *   n(0..3) = 1, n(4) = 5, n(128) = 3209, W[128] = 326.  table: the 4 R + 1 uint32 W[0..4 R], made on the host (src/_native.py:
+ *   lensblur_table); no kernel holds a closed form.  The kernel uses the low 24 bits of an entry and never uses one as an address: a
+ *   table that is not the one above cannot make it read outside its arguments, but the output is then unspecified.
+ * Gather.  For an output pixel p consider every pixel q of the same image with d2 = |q - p|^2 <= R^2; taps outside the image are
+ *   skipped (there is no wrap mode).  far = z(q) < z(p);  rho_e = far ? min(rho(q), rho(p)) : rho(q).  The tap counts iff
+ *   16 d2 <= rho_e^2; a counted tap adds W[rho_e] to den and W[rho_e] * c(q) to num_c for each of the three channels c.
+ *   So a nearer blurred pixel spreads over what is behind it, a farther pixel reaches p only as far as p's own blur allows, and an
+ *   in-focus foreground keeps a hard edge against a blurred background.  The self tap always counts: den > 0.
+ * Outputs.  out_rgb [n,h,w,3] uint8: out_c = (2 num_c + den) // (2 den).  out_coc [n,h,w] uint8: rho; the pointer may be NULL.
+ * Accumulators.  A tap at offset (dx, dy) adds at most W[ceil(4 sqrt(d2))]; summed over the disc at R = 32 that is 8,103,748, times 255
+ *   it is 2,066,455,740 < 2^31: den, the three num_c and 2 num_c + den fit uint32.
+ * Identities.  If every rho < 4 the output equals the image.  A constant-colour image comes back unchanged for any depth.
+ * A pixel's bits depend on its disc alone: not on its tile, its position in the batch or the launch; the NumPy model is
+ * tests/lensblur_cases.py.
+ * DS_EINVAL, before any launch: a null pointer other than out_coc; n, h or w <= 0; R outside 1..32, A outside 1..65535, band outside
+ * 0..65535; table not 4-byte aligned, focus or depth not 2-byte aligned (image, out_rgb and out_coc may have any alignment); an output
+ * overlapping image, depth, focus, table or the other output.  DS_EUNSUPPORTED: n > 65535 or h > 32 * 65535.  Asynchronous on `stream`;
+ * one kernel, no workspace; no kernel-timer kind (the kinds below DS_KT_RAGGED are used up).
+ */
+int ds_lensblur_u8(ds_ctx *ctx, const uint8_t *image, const uint16_t *depth, const uint16_t *focus, int n, int h, int w, int radius,
+                   int aperture, int band, int invert, const uint32_t *table, uint8_t *out_rgb, uint8_t *out_coc, void *stream);
+
+/*
  * ds_frame_luma_hist -- per-frame luma histograms of a uint8 clip: the input of video mode's scene-cut detector (the reference
  * leaves cut detection as a TODO, src/video_mode.py:114, and has no implementation; this comment is the definition).
  * frames [n,h,w,c] uint8, dense, ANY byte alignment -> hist [n,256] uint32: hist[f][v] = the number of pixels of frame f with Y == v.

@@ -27,7 +27,7 @@ EXPORTS = [
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
-    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_aomap_u16", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
+    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_aomap_u16", "ds_lensblur_u8", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
     "ds_preprocess_bicubic_rows", "ds_tokens_fixup", "ds_upsample_bicubic_to_f32", "ds_im2col3x3_s2_nhwc", "ds_dpt_head_front",
 ]
 
@@ -90,6 +90,7 @@ def lib():
             L.ds_sparse_bilateral_f32.argtypes = [vp, vp, vp, ci, ci, ci, ci, ctypes.c_float, vp, vp, vp, vp]
             L.ds_sparse_bilateral_jump_f32.argtypes = [vp, vp, ci, ci, ci, ctypes.c_float, vp, vp]
             L.ds_aomap_u16.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, cd, cd, ci, ci, vp, vp, vp]
+            L.ds_lensblur_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]
             L.ds_frame_luma_hist.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_smooth5_f32.argtypes = [vp, vp, ci, i64, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_joint_bilateral_u16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp]
@@ -349,8 +350,8 @@ def _tables_on(family, device, params, build, keep=4):
 
 
 def cached_tables(family):
-    """How many (device, params) the table cache holds for `family`: "bilateral", "depth_refine", "sparse_bilateral", "aomap", "stabilize"
-    or "lanczos"."""
+    """How many (device, params) the table cache holds for `family`: "bilateral", "depth_refine", "sparse_bilateral", "aomap", "lensblur",
+    "stabilize" or "lanczos"."""
     with _TABLES_LOCK:
         return len(_TABLES[family])
 
@@ -701,6 +702,127 @@ def aomap_u16(depth_u16, radius, directions, relief, intensity=1.0, invert=False
                               dir_start.data_ptr(), relief / 65535.0, intensity / directions, 1 if invert else 0, 1 if wrap else 0,
                               out.data_ptr(), out_f64.data_ptr() if want_f64 else None, _stream(depth_u16)))
     return (out, out_f64) if want_f64 else out
+
+
+# ---- lens blur from depth (csrc/ds_lensblur.hip; public interface: src/lensblur_generation.py) --------------------------------------
+LENSBLUR_MAX_RADIUS = 32
+
+
+def _lensblur_focus(focus):
+    """focus as an int in 0..65535 or ('point', fx, fy) with fx, fy floats in [0, 1]; raises TypeError / ValueError otherwise."""
+    if isinstance(focus, (tuple, list)):
+        if len(focus) != 3 or focus[0] != 'point':
+            raise TypeError
+        fx, fy = float(focus[1]), float(focus[2])
+        if not (0.0 <= fx <= 1.0 and 0.0 <= fy <= 1.0):
+            raise ValueError
+        return ('point', fx, fy)
+    if isinstance(focus, (str, bytes)):
+        raise TypeError
+    value, ok = _as_int(focus)
+    if not (ok and 0 <= value <= 65535):
+        raise ValueError
+    return value
+
+
+def lensblur_params(p):
+    """(radius, aperture, focus) or (radius, aperture, focus, band) as (int, float, focus, int), or ValueError: radius an integer in
+    1..32 and band an integer in 0..65535 (default 0; a bool is no integer); aperture a positive float, the blur radius in pixels that
+    a depth difference of the full uint16 range would get, with rint(4 aperture) in 1..65535; focus an integer in 0..65535 (a depth in
+    the map's own units) or ('point', fx, fy) with fx, fy in [0, 1] (the depth found at that position of each image).  Pure Python
+    (the funnel checks its option with it before any device work)."""
+    usage = "(radius, aperture, focus) or (radius, aperture, focus, band)"
+    try:
+        if isinstance(p, (str, bytes)):
+            raise TypeError
+        q = tuple(p)
+        if len(q) not in (3, 4):
+            raise TypeError
+        (radius, ok_r), aperture = _as_int(q[0]), float(q[1])
+        band, ok_b = _as_int(q[3]) if len(q) == 4 else (0, True)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("lensblur must be %s, got %r" % (usage, p)) from None
+    if not (ok_r and 1 <= radius <= LENSBLUR_MAX_RADIUS):
+        raise ValueError("lensblur: radius must be an integer in 1..%d, got %r" % (LENSBLUR_MAX_RADIUS, q[0]))
+    if not (0.0 < aperture < math.inf and 1 <= lensblur_quarter_pixels(aperture) <= 65535):
+        raise ValueError("lensblur: aperture must be a positive float with rint(4 * aperture) in 1..65535, got %r" % (q[1],))
+    try:
+        focus = _lensblur_focus(q[2])
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("lensblur: focus must be an integer in 0..65535 or ('point', fx, fy) with fx, fy in [0, 1], got %r"
+                         % (q[2],)) from None
+    if not (ok_b and 0 <= band <= 65535):
+        raise ValueError("lensblur: band must be an integer in 0..65535, got %r" % (q[3],))
+    return radius, aperture, focus, band
+
+
+def lensblur_quarter_pixels(aperture):
+    """A of ds_lensblur_u8 for an aperture in pixels per full uint16 range: rint(4 aperture), half to even."""
+    return int(np.rint(4.0 * aperture))
+
+
+def lensblur_table(radius):
+    """The weight table of ds_lensblur_u8 (include/depthstereo.h): a 1-tuple of uint32 [4 radius + 1], W[rho] = 2^20 // n(rho) with
+    n(rho) the number of integer (dx, dy) with 16 (dx^2 + dy^2) <= rho^2."""
+    dy, dx = np.mgrid[-radius:radius + 1, -radius:radius + 1]
+    d2 = np.sort((16 * (dx * dx + dy * dy)).ravel())
+    rho = np.arange(4 * radius + 1, dtype=np.int64)
+    return ((2**20 // np.searchsorted(d2, rho * rho, side='right')).astype(np.uint32),)
+
+
+def lensblur_u8(image_u8, depth_u16, radius, A, band, focus, invert=False, want_coc=False, out=None):
+    """Lens blur of uint8 images [n,h,w,3] (cuda) by their uint16 depth maps [n,h,w] (same device) -> uint8 [n,h,w,3]
+    (ds_lensblur_u8: the definition is in include/depthstereo.h).  radius 1..32: the largest blur radius in pixels; A 1..65535: quarter
+    pixels of blur radius per full uint16 range of depth difference; band 0..65535: depth differences up to it stay sharp.  focus: one
+    integer 0..65535 for every image, n of them, a uint16 cuda tensor [n], or ('point', fx, fy): each image's depth at
+    [min(h - 1, floor(fy h)), min(w - 1, floor(fx w))], read on the device without a host sync.  invert: black is near.  want_coc:
+    return (blurred, uint8 [n,h,w] circle of confusion in quarter pixels) instead.  out: write the image into this contiguous uint8
+    cuda tensor [n,h,w,3].  The weight table is made on the host, uploaded once and kept for the last 4 (device, radius)."""
+    torch = require_gpu()
+    (radius, ok_r), (A, ok_a), (band, ok_b) = _as_int(radius), _as_int(A), _as_int(band)
+    if not (ok_r and 1 <= radius <= LENSBLUR_MAX_RADIUS and ok_a and 1 <= A <= 65535 and ok_b and 0 <= band <= 65535):
+        raise DepthStereoError("lensblur_u8: radius must be an integer in 1..%d, A in 1..65535, band in 0..65535, got %r, %r, %r"
+                               % (LENSBLUR_MAX_RADIUS, radius, A, band))
+    _check_depth_guide("lensblur_u8", depth_u16, image_u8)
+    if image_u8.shape[3] != 3:
+        raise DepthStereoError("lensblur_u8: image must have 3 channels, got %s" % (tuple(image_u8.shape),))
+    image_u8, depth_u16 = image_u8.contiguous(), depth_u16.contiguous()
+    n, h, w = depth_u16.shape
+    if n == 0 or h == 0 or w == 0:
+        raise DepthStereoError("lensblur_u8: empty depth %s" % (tuple(depth_u16.shape),))
+    dev = depth_u16.device
+    if torch.is_tensor(focus):
+        if not (focus.dtype == torch.uint16 and focus.device == dev and tuple(focus.shape) == (n,)):
+            raise DepthStereoError("lensblur_u8: a focus tensor must be uint16 [%d] on the depth's device, got %s %s"
+                                   % (n, focus.dtype, tuple(focus.shape)))
+        focus_t = focus.contiguous()
+    else:
+        try:
+            many = isinstance(focus, (tuple, list, np.ndarray)) and not (len(focus) and isinstance(focus[0], str))
+            values = [_lensblur_focus(f) for f in focus] if many else _lensblur_focus(focus)
+            if many and (len(values) != n or any(isinstance(v, tuple) for v in values)):
+                raise ValueError
+        except (TypeError, ValueError, OverflowError):
+            raise DepthStereoError("lensblur_u8: focus must be an integer in 0..65535, %d of them, a uint16 tensor or ('point', fx, fy) "
+                                   "with fx, fy in [0, 1], got %r" % (n, focus)) from None
+        if many:
+            focus_t = torch.from_numpy(np.asarray(values, dtype=np.uint16)).to(dev)
+        elif isinstance(values, tuple):
+            focus_t = depth_u16[:, min(h - 1, int(values[2] * h)), min(w - 1, int(values[1] * w))].contiguous()
+        else:                                                             # (an int16 fill of the same 16 bits)
+            focus_t = torch.full((n,), values - 65536 if values >= 32768 else values, dtype=torch.int16, device=dev).view(torch.uint16)
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == dev and tuple(out.shape) == (n, h, w, 3)
+              and out.is_contiguous()):
+        raise DepthStereoError("lensblur_u8: out must be a contiguous uint8 tensor %s on the depth's device" % ((n, h, w, 3),))
+    (table,) = _tables_on("lensblur", dev, (radius,), lensblur_table)
+    coc = torch.empty((n, h, w), dtype=torch.uint8, device=dev) if want_coc else None
+    CALLS["ds_lensblur_u8"] += 1
+    _check(lib().ds_lensblur_u8(ctx_for(_dev_index(depth_u16)), image_u8.data_ptr(), depth_u16.data_ptr(), focus_t.data_ptr(), n, h, w,
+                                radius, A, band, 1 if invert else 0, table.data_ptr(), out.data_ptr(),
+                                coc.data_ptr() if want_coc else None, _stream(depth_u16)))
+    return (out, coc) if want_coc else out
 
 
 # ---- video mode (csrc/ds_video.hip; host half: src/video_mode.py) ------------------------------------------------------------------

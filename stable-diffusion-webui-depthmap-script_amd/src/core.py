@@ -439,7 +439,7 @@ def _mark(g, name, stream=None):
 
 
 def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=None, normalmap_wrap=False, normalmap_bilateral=None,
-                  depth_refine=None, depth_refine_wrap=False, aomap=None, aomap_wrap=False):
+                  depth_refine=None, depth_refine_wrap=False, aomap=None, aomap_wrap=False, lensblur=None):
     """Enqueue everything a group needs on the current stream -- H2D, network, post-processing, stereo, normal map, heat
     map, D2H into pinned buffers -- and return the handles; nothing here waits for the device except the post-processing
     branches that must know which predictions are flat (one sync per batch) and the percentile bisection of 'Outliers'."""
@@ -624,6 +624,16 @@ def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=Non
         if aomap is not None:                                                                        # ops['aomap'] (src/aomap_generation.py)
             from .aomap_generation import create_aomap_batch
             download(create_aomap_batch(d16, *aomap, wrap=aomap_wrap), "aomap")
+        if lensblur is not None:                                                                     # ops['lensblur'] (src/lensblur_generation.py)
+            # the pixels: already on the device where they are, chosen as depth_refine chooses its guide
+            if images[0].mode == "RGB" and img_t is not None:
+                pixels_t = img_t
+            elif rgb_t is not None:
+                pixels_t = rgb_t
+            else:
+                pixels_t = upload_pixels("lensblur", lambda im: np.asarray(im.convert("RGB"), dtype=np.uint8), rgb=images[0].mode == "RGB")
+            from .lensblur_generation import create_lensblur_batch
+            download(create_lensblur_batch(pixels_t, d16, *lensblur), "lensblur")
         _mark(g, "per-pixel kernels done")
         ready = torch.cuda.Event()
         ready.record()                                        # everything the copies read has been enqueued (main or post stream)
@@ -818,6 +828,8 @@ def _unit_tasks(g, j):
         tasks.append(("heatmap", lambda: ('heatmap', _to_pil(host["heatmap"].numpy()[j]))))
     if "aomap" in host:                                  # ops['aomap'] of this call: after the reference's outputs, before the mesh
         tasks.append(("aomap", lambda: ('aomap', _to_pil(host["aomap"].numpy()[j]))))
+    if "lensblur" in host:                               # ops['lensblur'] of this call: after 'aomap', before the mesh
+        tasks.append(("lensblur", lambda: ('lensblur', _to_pil(host["lensblur"].numpy()[j]))))
     return tasks
 
 
@@ -940,9 +952,16 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
             raise ValueError("ops['aomap_wrap'] must be True, False or 'tiling', got %r" % (aomap_wrap,))
         aomap_wrap = bool(inp[go.TILING_MODE])
     aomap_wrap = bool(aomap_wrap)
+    # ops['lensblur'] (not in the reference): (radius, aperture, focus[, band]) = a synthetic shallow depth of field of the input image
+    # by the uint16 depth map the stereo warp reads -- behind depth_refine, the refined one -- (src/lensblur_generation.py), yielded as
+    # (i, 'lensblur', image) after 'aomap'; the map is white = near, so invert stays off.  Absent / None = off, and then the call makes
+    # the launches, uploads and bytes it always made.  An option of THIS call, checked here before any device work.
+    lensblur = ops.get('lensblur')
+    if lensblur is not None:
+        lensblur = _native.lensblur_params(lensblur)
     model_holder.update_settings(**{k: v for k, v in ops.items()
                                     if k not in ('normalmap_wrap', 'normalmap_bilateral', 'depth_refine', 'depth_refine_wrap', 'aomap',
-                                                 'aomap_wrap')})
+                                                 'aomap_wrap', 'lensblur')})
 
     torch = _native.require_gpu()        # the hot path has no CPU implementation, whatever COMPUTE_DEVICE says
     device = torch.device('cuda', torch.cuda.current_device())
@@ -973,7 +992,7 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
             try:
                 _t0 = _time.perf_counter()
                 launched, failure = _launch_group(gi & 1, idxs, inputimages, inputdepthmaps, inp, device, stats, normalmap_wrap,
-                                                  normalmap_bilateral, depth_refine, depth_refine_wrap, aomap, aomap_wrap), None
+                                                  normalmap_bilateral, depth_refine, depth_refine_wrap, aomap, aomap_wrap, lensblur), None
                 stats["launch"] = stats.get("launch", 0.0) + (_time.perf_counter() - _t0)
             except Exception as e:          # noqa: BLE001 -- re-raised below, after the results that precede it
                 launched, failure = None, e
