@@ -376,6 +376,45 @@ int ds_lensblur_u8(ds_ctx *ctx, const uint8_t *image, const uint16_t *depth, con
                    int aperture, int band, int invert, const uint32_t *table, uint8_t *out_rgb, uint8_t *out_coc, void *stream);
 
 /*
+ * ds_parallax_u8 -- parallax frames from depth: F novel views of each of n images by its uint16 depth map, for small camera motions.
+ * Every source pixel is pushed to where it lands in the new view (splat), the nearest pixel wins each target pixel, and the
+ * disocclusion holes are closed from the background side (resolve).  The reference renders such clips from a layered, inpainted mesh;
+ * this comment is the definition, and the only normative text.  Everything is an integer, and the depth test is a maximum, so the
+ * result does not depend on the order in which anything runs.  `>>` is an arithmetic shift: a floor.
+ * Inputs.  image [n,h,w,3] uint8.  depth [n,h,w] uint16.  focus [n] uint16, on the device, in the units of depth as stored.
+ *   poses [F,3] int32 (tx, ty, tz), on the device: tx, ty in sixteenths of a pixel of shift per full uint16 range of depth difference,
+ *   tz in 1/4096 of scale per full range; each component is clamped to -1024..1024 in the kernel (a bad device array can then not
+ *   address outside the arguments; the host wrapper rejects such poses before that).  fill G in 1..64.  Flag invert.
+ *   Workspace keys [n,F,h,w] uint64, any content: the entry point clears it.
+ * Nearness.  z = depth, or 65535 - depth with invert != 0; z0 = focus, mapped the same way; e = z - z0, |e| <= 65535.
+ * Landing point of source pixel (x, y) under pose k, in sixteenths of a pixel with the pixel centre at 16 x + 8:
+ *   sx = (e * tx + 32768) >> 16;  sy = (e * ty + 32768) >> 16;  m = (e * tz + 32768) >> 16;
+ *   cx = 16 x + 8 - 8 w;  cy = 16 y + 8 - 8 h;
+ *   ux = 16 x + 8 + sx + ((cx * m + 2048) >> 12);  uy = 16 y + 8 + sy + ((cy * m + 2048) >> 12).
+ *   |e * t| < 2^26 and |c * m| < 2^28: int32 suffices.
+ * Footprint, 1.5 pixels wide, so that a stretch of up to 1.5 leaves no cracks: target columns X0..X1 with X0 = (ux - 5) >> 4 and
+ *   X1 = ((ux + 19) >> 4) - 1 -- one column, or two exactly when (ux - 8) mod 16 is in 5..12 -- and rows Y0..Y1 likewise from uy.
+ *   Targets outside the image are dropped.  At zero displacement the footprint is the pixel itself.
+ * Splat.  key = ((z + 1) << 32) | (y w + x); keys starts at 0 everywhere; every covered target takes the maximum of the keys offered
+ *   to it.  So the nearer pixel wins, among equal z the larger source index, and 0 means that nothing landed.
+ * Resolve, per target (X, Y) of view k.  key != 0: out = image[key & 0xFFFFFFFF] (a pixel index of the same image), mask = 0.
+ *   Otherwise scan left, right, up and down, in that order, each over steps 1..G and not beyond the image border; the first target
+ *   with key != 0 is the direction's candidate.  The candidate with the smallest key >> 32 -- the farthest: a disocclusion belongs to
+ *   the background -- gives its source pixel, the earlier direction on a tie, and mask = 1.  No candidate: out = image[Y][X] of the
+ *   same image, mask = 2.
+ * Outputs.  out [n,F,h,w,3] uint8.  out_mask [n,F,h,w] uint8; the pointer may be NULL.
+ * Identities.  Pose (0, 0, 0) returns the image with an all-zero mask, for any depth.  A depth equal to the focus everywhere returns
+ * the image for any pose.  Views and images are independent of each other.  The NumPy model is tests/parallax_cases.py.
+ * DS_EINVAL, before any launch: a null pointer other than out_mask; n, h, w or F <= 0; fill outside 1..64; keys not 8-byte aligned,
+ * poses not 4-byte aligned, depth or focus not 2-byte aligned (image, out and out_mask may have any alignment).  Then DS_EUNSUPPORTED:
+ * n * F > 65535, or h or w > 16384.  Then DS_EINVAL: out, out_mask or keys overlapping an input or each other.  Asynchronous on
+ * `stream`: a memset of keys on that stream and two launches, so the call is safe under graph capture.  No kernel-timer kind; with
+ * ds_profile_enable the context's two event pairs bracket the splat and the resolve launch, and ds_profile_last_ms returns them.
+ */
+int ds_parallax_u8(ds_ctx *ctx, const uint8_t *image, const uint16_t *depth, const uint16_t *focus, int n, int h, int w,
+                   const int32_t *poses, int F, int fill, int invert, void *keys, uint8_t *out, uint8_t *out_mask, void *stream);
+
+/*
  * ds_frame_luma_hist -- per-frame luma histograms of a uint8 clip: the input of video mode's scene-cut detector (the reference
  * leaves cut detection as a TODO, src/video_mode.py:114, and has no implementation; this comment is the definition).
  * frames [n,h,w,c] uint8, dense, ANY byte alignment -> hist [n,256] uint32: hist[f][v] = the number of pixels of frame f with Y == v.

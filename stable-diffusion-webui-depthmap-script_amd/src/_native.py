@@ -27,7 +27,7 @@ EXPORTS = [
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
-    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_aomap_u16", "ds_lensblur_u8", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
+    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_aomap_u16", "ds_lensblur_u8", "ds_parallax_u8", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
     "ds_preprocess_bicubic_rows", "ds_tokens_fixup", "ds_upsample_bicubic_to_f32", "ds_im2col3x3_s2_nhwc", "ds_dpt_head_front",
 ]
 
@@ -91,6 +91,7 @@ def lib():
             L.ds_sparse_bilateral_jump_f32.argtypes = [vp, vp, ci, ci, ci, ctypes.c_float, vp, vp]
             L.ds_aomap_u16.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, cd, cd, ci, ci, vp, vp, vp]
             L.ds_lensblur_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]
+            L.ds_parallax_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, ci, vp, vp, vp, vp]
             L.ds_frame_luma_hist.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_smooth5_f32.argtypes = [vp, vp, ci, i64, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_joint_bilateral_u16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp]
@@ -725,6 +726,35 @@ def _lensblur_focus(focus):
     return value
 
 
+def _focus_on_device(name, focus, depth_u16):
+    """The focus depths of a dense uint16 cuda batch [n,h,w] as a uint16 tensor [n] on its device, without a host sync.  focus: one
+    integer 0..65535 for every image, n of them, a uint16 cuda tensor [n], or ('point', fx, fy): each image's depth at
+    [min(h - 1, floor(fy h)), min(w - 1, floor(fx w))].  Anything else is a DepthStereoError in `name`'s name.  Shared by lensblur_u8
+    and parallax_u8."""
+    torch = _torch()
+    n, h, w = depth_u16.shape
+    dev = depth_u16.device
+    if torch.is_tensor(focus):
+        if not (focus.dtype == torch.uint16 and focus.device == dev and tuple(focus.shape) == (n,)):
+            raise DepthStereoError("%s: a focus tensor must be uint16 [%d] on the depth's device, got %s %s"
+                                   % (name, n, focus.dtype, tuple(focus.shape)))
+        return focus.contiguous()
+    try:
+        many = isinstance(focus, (tuple, list, np.ndarray)) and not (len(focus) and isinstance(focus[0], str))
+        values = [_lensblur_focus(f) for f in focus] if many else _lensblur_focus(focus)
+        if many and (len(values) != n or any(isinstance(v, tuple) for v in values)):
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise DepthStereoError("%s: focus must be an integer in 0..65535, %d of them, a uint16 tensor or ('point', fx, fy) "
+                               "with fx, fy in [0, 1], got %r" % (name, n, focus)) from None
+    if many:
+        return torch.from_numpy(np.asarray(values, dtype=np.uint16)).to(dev)
+    if isinstance(values, tuple):
+        return depth_u16[:, min(h - 1, int(values[2] * h)), min(w - 1, int(values[1] * w))].contiguous()
+    # (an int16 fill of the same 16 bits)
+    return torch.full((n,), values - 65536 if values >= 32768 else values, dtype=torch.int16, device=dev).view(torch.uint16)
+
+
 def lensblur_params(p):
     """(radius, aperture, focus) or (radius, aperture, focus, band) as (int, float, focus, int), or ValueError: radius an integer in
     1..32 and band an integer in 0..65535 (default 0; a bool is no integer); aperture a positive float, the blur radius in pixels that
@@ -791,26 +821,7 @@ def lensblur_u8(image_u8, depth_u16, radius, A, band, focus, invert=False, want_
     if n == 0 or h == 0 or w == 0:
         raise DepthStereoError("lensblur_u8: empty depth %s" % (tuple(depth_u16.shape),))
     dev = depth_u16.device
-    if torch.is_tensor(focus):
-        if not (focus.dtype == torch.uint16 and focus.device == dev and tuple(focus.shape) == (n,)):
-            raise DepthStereoError("lensblur_u8: a focus tensor must be uint16 [%d] on the depth's device, got %s %s"
-                                   % (n, focus.dtype, tuple(focus.shape)))
-        focus_t = focus.contiguous()
-    else:
-        try:
-            many = isinstance(focus, (tuple, list, np.ndarray)) and not (len(focus) and isinstance(focus[0], str))
-            values = [_lensblur_focus(f) for f in focus] if many else _lensblur_focus(focus)
-            if many and (len(values) != n or any(isinstance(v, tuple) for v in values)):
-                raise ValueError
-        except (TypeError, ValueError, OverflowError):
-            raise DepthStereoError("lensblur_u8: focus must be an integer in 0..65535, %d of them, a uint16 tensor or ('point', fx, fy) "
-                                   "with fx, fy in [0, 1], got %r" % (n, focus)) from None
-        if many:
-            focus_t = torch.from_numpy(np.asarray(values, dtype=np.uint16)).to(dev)
-        elif isinstance(values, tuple):
-            focus_t = depth_u16[:, min(h - 1, int(values[2] * h)), min(w - 1, int(values[1] * w))].contiguous()
-        else:                                                             # (an int16 fill of the same 16 bits)
-            focus_t = torch.full((n,), values - 65536 if values >= 32768 else values, dtype=torch.int16, device=dev).view(torch.uint16)
+    focus_t = _focus_on_device("lensblur_u8", focus, depth_u16)
     if out is None:
         out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
     elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == dev and tuple(out.shape) == (n, h, w, 3)
@@ -823,6 +834,178 @@ def lensblur_u8(image_u8, depth_u16, radius, A, band, focus, invert=False, want_
                                 radius, A, band, 1 if invert else 0, table.data_ptr(), out.data_ptr(),
                                 coc.data_ptr() if want_coc else None, _stream(depth_u16)))
     return (out, coc) if want_coc else out
+
+
+# ---- parallax frames from depth (csrc/ds_parallax.hip; public interface: src/parallax_generation.py) ---------------------------------
+PARALLAX_MAX_FRAMES = 256
+PARALLAX_MAX_SHIFT = 64.0            # pixels per full uint16 range of depth difference: 1024 sixteenths
+PARALLAX_MAX_ZOOM = 0.25             # scale fraction per full range: 1024 / 4096
+PARALLAX_MAX_FILL = 64
+PARALLAX_POSE_MAX = 1024
+PARALLAX_PATHS = ('circle', 'line')
+PARALLAX_WS_BYTES = 256 << 20        # the key workspace of one ds_parallax_u8 call; more views than fit are rendered in several calls
+
+
+def _as_float(v, limit):
+    """float(v) for a number with |v| <= limit; a bool, a string, a NaN or an out-of-range value raises TypeError / ValueError."""
+    if isinstance(v, (bool, np.bool_, str, bytes)):
+        raise TypeError
+    f = float(v)
+    if not abs(f) <= limit:              # (a NaN fails this too)
+        raise ValueError
+    return f
+
+
+def _parallax_frames(frames):
+    if isinstance(frames, (str, bytes)):
+        raise TypeError
+    value, ok = _as_int(frames)
+    if not (ok and 1 <= value <= PARALLAX_MAX_FRAMES):
+        raise ValueError
+    return value
+
+
+def parallax_path(path, frames, shift_x, shift_y, zoom):
+    """The camera path as float64 [F,3] of (x in pixels, y in pixels, z as a scale fraction), each per full uint16 range of depth
+    difference.  path 'circle': (X cos a_k, Y sin a_k, Z cos a_k) with a_k = 2 pi k / F (Y = 0 is the reference's "swing");
+    'line': from (-X, -Y, -Z) to (X, Y, Z), linear in k / (F - 1), the origin for F = 1; X, Y, Z = shift_x, shift_y, zoom.  Or an
+    explicit array [F,3] of such triples: frames must then be None or F, and shift and zoom are not used.  Limits: |x|, |y| <= 64,
+    |z| <= 0.25, 1 <= F <= 256.  Raises ValueError."""
+    if isinstance(path, str):
+        if path not in PARALLAX_PATHS:
+            raise ValueError("parallax: path must be one of %r or an array [F,3], got %r" % (PARALLAX_PATHS, path))
+        try:
+            F = _parallax_frames(frames)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("parallax: frames must be an integer in 1..%d, got %r" % (PARALLAX_MAX_FRAMES, frames)) from None
+        try:
+            X, Y = _as_float(shift_x, PARALLAX_MAX_SHIFT), _as_float(shift_y, PARALLAX_MAX_SHIFT)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("parallax: shift must be two numbers with |shift| <= %g pixels, got %r, %r"
+                             % (PARALLAX_MAX_SHIFT, shift_x, shift_y)) from None
+        try:
+            Z = _as_float(zoom, PARALLAX_MAX_ZOOM)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("parallax: zoom must be a number with |zoom| <= %g, got %r" % (PARALLAX_MAX_ZOOM, zoom)) from None
+        k = np.arange(F, dtype=np.float64)
+        if path == 'circle':
+            a = 2.0 * np.pi * k / F
+            return np.stack([X * np.cos(a), Y * np.sin(a), Z * np.cos(a)], axis=1)
+        t = 2.0 * k / (F - 1) - 1.0 if F > 1 else np.zeros(1)
+        return np.stack([X * t, Y * t, Z * t], axis=1)
+    try:
+        if isinstance(path, bytes) or path is None:
+            raise TypeError
+        arr = np.asarray(path)
+        if arr.dtype.kind not in 'iuf' or arr.ndim != 2 or arr.shape[1] != 3 or not 1 <= arr.shape[0] <= PARALLAX_MAX_FRAMES:
+            raise TypeError
+        arr = arr.astype(np.float64)
+        if frames is not None and _parallax_frames(frames) != arr.shape[0]:
+            raise ValueError
+        if not (np.abs(arr[:, :2]) <= PARALLAX_MAX_SHIFT).all() or not (np.abs(arr[:, 2]) <= PARALLAX_MAX_ZOOM).all():
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("parallax: an explicit path must be a numeric array [F,3] with 1 <= F <= %d (frames None or F), |x|, |y| <= %g "
+                         "and |z| <= %g, got %r" % (PARALLAX_MAX_FRAMES, PARALLAX_MAX_SHIFT, PARALLAX_MAX_ZOOM, path)) from None
+    return arr
+
+
+def parallax_poses(path, frames, shift_x, shift_y, zoom):
+    """poses of ds_parallax_u8 (include/depthstereo.h) for a camera path (parallax_path): int32 [F,3] of tx = rint(16 x),
+    ty = rint(16 y), tz = rint(4096 z), half to even; every component within +-1024.  Raises ValueError."""
+    p = parallax_path(path, frames, shift_x, shift_y, zoom)
+    return np.rint(p * np.array([16.0, 16.0, 4096.0])).astype(np.int32)
+
+
+def parallax_params(p):
+    """(path, frames, shift_x, shift_y, zoom), (..., focus) or (..., focus, fill) as (path, int, float, float, float, focus, int), or
+    ValueError.  path, frames, shift_x, shift_y, zoom: what parallax_path takes (an explicit path comes back as a float64 array,
+    frames as its length); focus: an integer in 0..65535 or ('point', fx, fy) with fx, fy in [0, 1] (default ('point', 0.5, 0.5));
+    fill: an integer in 1..64, the reach in pixels of the hole filling (default 32; a bool is no integer).  Pure Python (the funnel
+    checks its option with it before any device work)."""
+    usage = "(path, frames, shift_x, shift_y, zoom[, focus[, fill]])"
+    try:
+        if isinstance(p, (str, bytes)):
+            raise TypeError
+        q = tuple(p)
+        if len(q) not in (5, 6, 7):
+            raise TypeError
+    except TypeError:
+        raise ValueError("parallax must be %s, got %r" % (usage, p)) from None
+    path, frames = q[0], q[1]
+    track = parallax_path(path, frames, q[2], q[3], q[4])
+    if not isinstance(path, str):
+        path, shift_x, shift_y, zoom = track, 0.0, 0.0, 0.0
+    else:
+        shift_x, shift_y, zoom = float(q[2]), float(q[3]), float(q[4])
+    try:
+        focus = _lensblur_focus(q[5]) if len(q) > 5 else ('point', 0.5, 0.5)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("parallax: focus must be an integer in 0..65535 or ('point', fx, fy) with fx, fy in [0, 1], got %r"
+                         % (q[5],)) from None
+    try:
+        fill, ok = _as_int(q[6]) if len(q) > 6 else (32, True)
+        if not (ok and 1 <= fill <= PARALLAX_MAX_FILL):
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("parallax: fill must be an integer in 1..%d, got %r" % (PARALLAX_MAX_FILL, q[6])) from None
+    return path, len(track), shift_x, shift_y, zoom, focus, fill
+
+
+def parallax_u8(image_u8, depth_u16, poses, focus, fill, invert=False, want_mask=False, out=None):
+    """F novel views of uint8 images [n,h,w,3] (cuda) by their uint16 depth maps [n,h,w] (same device) -> uint8 [n,F,h,w,3]
+    (ds_parallax_u8: the definition is in include/depthstereo.h).  poses: a host integer array [F,3] of (tx, ty, tz) within +-1024
+    (parallax_poses makes one); anything else is refused here, before the kernel would clamp it.  focus: what lensblur_u8 takes: one
+    integer 0..65535 for every image, n of them, a uint16 cuda tensor [n], or ('point', fx, fy).  fill 1..64: the reach of the hole
+    filling.  invert: black is near.  want_mask: return (frames, uint8 [n,F,h,w]: 0 = a pixel landed, 1 = filled, 2 = nothing found)
+    instead.  out: write the frames into this contiguous uint8 cuda tensor [n,F,h,w,3].  The key workspace (8 bytes per target pixel)
+    comes from torch's allocator; when all F views need more than PARALLAX_WS_BYTES the views are rendered in several calls."""
+    torch = require_gpu()
+    try:
+        fill, ok = _as_int(fill)
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not (ok and 1 <= fill <= PARALLAX_MAX_FILL):
+        raise DepthStereoError("parallax_u8: fill must be an integer in 1..%d, got %r" % (PARALLAX_MAX_FILL, fill))
+    pose_arr = None if torch.is_tensor(poses) or isinstance(poses, (str, bytes)) or poses is None else np.asarray(poses)
+    if (pose_arr is None or pose_arr.dtype.kind not in 'iu' or pose_arr.ndim != 2 or pose_arr.shape[1] != 3 or pose_arr.shape[0] == 0
+            or int(np.abs(pose_arr.astype(np.int64)).max()) > PARALLAX_POSE_MAX):
+        raise DepthStereoError("parallax_u8: poses must be a host integer array [F,3] with F >= 1 and every component within +-%d, got %r"
+                               % (PARALLAX_POSE_MAX, poses))
+    _check_depth_guide("parallax_u8", depth_u16, image_u8)
+    if image_u8.shape[3] != 3:
+        raise DepthStereoError("parallax_u8: image must have 3 channels, got %s" % (tuple(image_u8.shape),))
+    image_u8, depth_u16 = image_u8.contiguous(), depth_u16.contiguous()
+    n, h, w = depth_u16.shape
+    if n == 0 or h == 0 or w == 0:
+        raise DepthStereoError("parallax_u8: empty depth %s" % (tuple(depth_u16.shape),))
+    F = pose_arr.shape[0]
+    dev = depth_u16.device
+    focus_t = _focus_on_device("parallax_u8", focus, depth_u16)
+    if out is None:
+        out = torch.empty((n, F, h, w, 3), dtype=torch.uint8, device=dev)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == dev and tuple(out.shape) == (n, F, h, w, 3)
+              and out.is_contiguous()):
+        raise DepthStereoError("parallax_u8: out must be a contiguous uint8 tensor %s on the depth's device" % ((n, F, h, w, 3),))
+    mask = torch.empty((n, F, h, w), dtype=torch.uint8, device=dev) if want_mask else None
+    poses_t = torch.from_numpy(np.ascontiguousarray(pose_arr, dtype=np.int32)).to(dev)
+    per_call = max(1, min(F, PARALLAX_WS_BYTES // (8 * n * h * w), 65535 // n))      # views per call (the entry point's n * F <= 65535)
+    keys = torch.empty((n * per_call * h * w,), dtype=torch.int64, device=dev)
+    ctx, st = ctx_for(_dev_index(depth_u16)), _stream(depth_u16)
+    for k0 in range(0, F, per_call):
+        k1 = min(F, k0 + per_call)
+        whole = n == 1 or (k0 == 0 and k1 == F)                          # out[:, k0:k1] is dense: the call writes it in place
+        part = out[:, k0:k1] if whole else torch.empty((n, k1 - k0, h, w, 3), dtype=torch.uint8, device=dev)
+        part_mask = None if mask is None else mask[:, k0:k1] if whole else torch.empty((n, k1 - k0, h, w), dtype=torch.uint8, device=dev)
+        CALLS["ds_parallax_u8"] += 1
+        _check(lib().ds_parallax_u8(ctx, image_u8.data_ptr(), depth_u16.data_ptr(), focus_t.data_ptr(), n, h, w,
+                                    poses_t.data_ptr() + 12 * k0, k1 - k0, fill, 1 if invert else 0, keys.data_ptr(), part.data_ptr(),
+                                    part_mask.data_ptr() if part_mask is not None else None, st))
+        if not whole:
+            out[:, k0:k1].copy_(part)
+            if mask is not None:
+                mask[:, k0:k1].copy_(part_mask)
+    return (out, mask) if want_mask else out
 
 
 # ---- video mode (csrc/ds_video.hip; host half: src/video_mode.py) ------------------------------------------------------------------

@@ -439,7 +439,7 @@ def _mark(g, name, stream=None):
 
 
 def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=None, normalmap_wrap=False, normalmap_bilateral=None,
-                  depth_refine=None, depth_refine_wrap=False, aomap=None, aomap_wrap=False, lensblur=None):
+                  depth_refine=None, depth_refine_wrap=False, aomap=None, aomap_wrap=False, lensblur=None, parallax=None):
     """Enqueue everything a group needs on the current stream -- H2D, network, post-processing, stereo, normal map, heat
     map, D2H into pinned buffers -- and return the handles; nothing here waits for the device except the post-processing
     branches that must know which predictions are flat (one sync per batch) and the percentile bisection of 'Outliers'."""
@@ -634,6 +634,15 @@ def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=Non
                 pixels_t = upload_pixels("lensblur", lambda im: np.asarray(im.convert("RGB"), dtype=np.uint8), rgb=images[0].mode == "RGB")
             from .lensblur_generation import create_lensblur_batch
             download(create_lensblur_batch(pixels_t, d16, *lensblur), "lensblur")
+        if parallax is not None:                                                                     # ops['parallax'] (src/parallax_generation.py)
+            if images[0].mode == "RGB" and img_t is not None:                                        # the pixels: as for 'lensblur'
+                pixels_t = img_t
+            elif rgb_t is not None:
+                pixels_t = rgb_t
+            else:
+                pixels_t = upload_pixels("parallax_in", lambda im: np.asarray(im.convert("RGB"), dtype=np.uint8), rgb=images[0].mode == "RGB")
+            from .parallax_generation import create_parallax_batch
+            download(create_parallax_batch(pixels_t, d16, _native.parallax_poses(*parallax[:5]), parallax[5], parallax[6]), "parallax")
         _mark(g, "per-pixel kernels done")
         ready = torch.cuda.Event()
         ready.record()                                        # everything the copies read has been enqueued (main or post stream)
@@ -830,6 +839,8 @@ def _unit_tasks(g, j):
         tasks.append(("aomap", lambda: ('aomap', _to_pil(host["aomap"].numpy()[j]))))
     if "lensblur" in host:                               # ops['lensblur'] of this call: after 'aomap', before the mesh
         tasks.append(("lensblur", lambda: ('lensblur', _to_pil(host["lensblur"].numpy()[j]))))
+    if "parallax" in host:                               # ops['parallax'] of this call: the frames of unit j, after 'lensblur', before the mesh
+        tasks.append(("parallax", lambda: ('parallax', [_to_pil(f) for f in host["parallax"].numpy()[j]])))
     return tasks
 
 
@@ -959,9 +970,17 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
     lensblur = ops.get('lensblur')
     if lensblur is not None:
         lensblur = _native.lensblur_params(lensblur)
+    # ops['parallax'] (the reference renders such clips from its inpainted mesh): (path, frames, shift_x, shift_y, zoom[, focus[, fill]])
+    # = camera-motion frames of the input image by the uint16 depth map the stereo warp reads -- behind depth_refine, the refined one --
+    # (src/parallax_generation.py), yielded as (i, 'parallax', [frames]) after 'lensblur'; the map is white = near, so invert stays off.
+    # Absent / None = off, and then the call makes the launches, uploads and bytes it always made.  An option of THIS call, checked
+    # here before any device work.
+    parallax = ops.get('parallax')
+    if parallax is not None:
+        parallax = _native.parallax_params(parallax)
     model_holder.update_settings(**{k: v for k, v in ops.items()
                                     if k not in ('normalmap_wrap', 'normalmap_bilateral', 'depth_refine', 'depth_refine_wrap', 'aomap',
-                                                 'aomap_wrap', 'lensblur')})
+                                                 'aomap_wrap', 'lensblur', 'parallax')})
 
     torch = _native.require_gpu()        # the hot path has no CPU implementation, whatever COMPUTE_DEVICE says
     device = torch.device('cuda', torch.cuda.current_device())
@@ -992,7 +1011,7 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
             try:
                 _t0 = _time.perf_counter()
                 launched, failure = _launch_group(gi & 1, idxs, inputimages, inputdepthmaps, inp, device, stats, normalmap_wrap,
-                                                  normalmap_bilateral, depth_refine, depth_refine_wrap, aomap, aomap_wrap, lensblur), None
+                                                  normalmap_bilateral, depth_refine, depth_refine_wrap, aomap, aomap_wrap, lensblur, parallax), None
                 stats["launch"] = stats.get("launch", 0.0) + (_time.perf_counter() - _t0)
             except Exception as e:          # noqa: BLE001 -- re-raised below, after the results that precede it
                 launched, failure = None, e
