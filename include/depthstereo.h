@@ -415,6 +415,45 @@ int ds_parallax_u8(ds_ctx *ctx, const uint8_t *image, const uint16_t *depth, con
                    const int32_t *poses, int F, int fill, int invert, void *keys, uint8_t *out, uint8_t *out_mask, void *stream);
 
 /*
+ * ds_autostereogram_u8 -- autostereograms from depth: the single-image stereogram ("magic eye": random dots, or a texture) of each of
+ * n uint16 depth maps.  The depth map alone decides which pixels of a row must share a colour: every column links the two columns in
+ * which the two eyes see it, and a pixel takes its colour from the connected component it ends up in.  The reference has no
+ * counterpart; this comment is the definition, and the only normative text.  Everything is an integer, every row is independent, and a
+ * component's representative is a maximum, so the result does not depend on the order in which anything runs.
+ * Inputs.  depth [n,h,w] uint16, white = near.  period P in 16..512: the on-screen separation in pixels of the far plane, the width of
+ *   a strip.  m in 1..128: the depth factor mu = m / 256 (mu = 1/3, m = 85: the near plane sits a third of the way from the screen to
+ *   the eyes).  mode 0 = coloured dots, 1 = black / white dots, 2 = a pattern tile [ph,pw,3] uint8 on the device, ph and pw in 1..4096
+ *   (with mode 0 or 1, tile, ph and pw are not looked at, and tile may be NULL).  seed: any uint32.  Flag invert.
+ * Nearness.  z = depth, or 65535 - depth with invert != 0.  A = 256 * 65535.
+ * Separation of a column of nearness z, rounded half up, in 64-bit integers:
+ *   den = 2 A - m z;  num = 2 P (A - m z);  s(z) = (2 num + den) / (2 den).
+ *   s(0) = P and s never increases with z; P = 96, m = 85 gives 96, 92, 87, 82, 77 at z = 0, 16384, 32768, 49152, 65535.
+ * Link.  Column x, with s = s(z[x]), l = x - (s >> 1) and r = l + s, offers the undirected link {l, r} when 0 <= l, r < w and x is
+ *   visible.
+ * Visibility (hidden-surface removal).  k = 2 A - m z[x].  For t = 1, 2, ...: zt = z[x] + (2 t k) / (m 2 P), an integer division; stop
+ *   at the first t with zt >= 65535 (after at most m P / 512 + 1 steps: at most 129).  x is hidden when for some t before that
+ *   z[x - t] >= zt or z[x + t] >= zt; columns outside the row occlude nothing.
+ * Colour.  rep(x) = the largest column index in the connected component of x under all links offered in its row.  Pixel (y, x):
+ *   modes 0 and 1: hash = lowbias32(seed ^ (y * 0x9E3779B1) ^ (rep * 0x85EBCA77)) in uint32 wrap-around arithmetic, lowbias32(v) being
+ *     v ^= v >> 16; v *= 0x7FEB352D; v ^= v >> 15; v *= 0x846CA68B; v ^= v >> 16.
+ *     Mode 0: R, G, B = bits 0-7, 8-15, 16-23 of hash.  Mode 1: 255 * (hash >> 31) on all three channels.
+ *   mode 2: tile[y mod ph][rep mod pw].
+ * Output.  out [n,h,w,3] uint8, at any byte address.  The image index does not enter: an image's output does not depend on its batch.
+ * Identities.  rep(x) >= x.  Both ends of every offered link have one colour.  On a flat map out[y][x] == out[y][x + s] for every x
+ * with x + s < w.  The NumPy model is tests/autostereogram_cases.py.
+ * DS_EINVAL, before any launch: a null ctx, depth or out, a null tile with mode 2; n, h or w <= 0; period outside 16..512, m outside
+ * 1..128, mode outside 0..2, with mode 2 ph or pw outside 1..4096; depth not 2-byte aligned.  Then DS_EUNSUPPORTED: h or w > 16384, or
+ * n > 65535.  Then DS_EINVAL: out overlapping depth or (mode 2) tile.  Asynchronous on `stream`: one launch, one workgroup per image
+ * row, no workspace and no global atomics, so the call is safe under graph capture.  No kernel-timer kind.
+ * ds_autostereogram_rounds_u8 is the same call, and writes into rounds [n,h] uint16 (not NULL, 2-byte aligned, overlapping nothing) how
+ * many rounds of label propagation each row's workgroup made, the last, idle one included (tools/autostereogram_ab.py reports them).
+ */
+int ds_autostereogram_u8(ds_ctx *ctx, const uint16_t *depth, int n, int h, int w, int period, int m, int mode, uint32_t seed,
+                         const uint8_t *tile, int ph, int pw, int invert, uint8_t *out, void *stream);
+int ds_autostereogram_rounds_u8(ds_ctx *ctx, const uint16_t *depth, int n, int h, int w, int period, int m, int mode, uint32_t seed,
+                                const uint8_t *tile, int ph, int pw, int invert, uint8_t *out, uint16_t *rounds, void *stream);
+
+/*
  * ds_frame_luma_hist -- per-frame luma histograms of a uint8 clip: the input of video mode's scene-cut detector (the reference
  * leaves cut detection as a TODO, src/video_mode.py:114, and has no implementation; this comment is the definition).
  * frames [n,h,w,c] uint8, dense, ANY byte alignment -> hist [n,256] uint32: hist[f][v] = the number of pixels of frame f with Y == v.

@@ -27,7 +27,7 @@ EXPORTS = [
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
-    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_aomap_u16", "ds_lensblur_u8", "ds_parallax_u8", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
+    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_aomap_u16", "ds_lensblur_u8", "ds_parallax_u8", "ds_autostereogram_u8", "ds_autostereogram_rounds_u8", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
     "ds_preprocess_bicubic_rows", "ds_tokens_fixup", "ds_upsample_bicubic_to_f32", "ds_im2col3x3_s2_nhwc", "ds_dpt_head_front",
 ]
 
@@ -92,7 +92,9 @@ def lib():
             L.ds_aomap_u16.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, cd, cd, ci, ci, vp, vp, vp]
             L.ds_lensblur_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]
             L.ds_parallax_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, ci, vp, vp, vp, vp]
-            L.ds_frame_luma_hist.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
+            L.ds_autostereogram_u8.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ctypes.c_uint32, vp, ci, ci, ci, vp, vp]
+            L.ds_autostereogram_rounds_u8.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ctypes.c_uint32, vp, ci, ci, ci, vp, vp, vp]
+            L.ds_frame_luma_hist.argtypes =[vp, vp, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_smooth5_f32.argtypes = [vp, vp, ci, i64, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_joint_bilateral_u16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp]
             L.ds_depth_to_u16.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp]
@@ -1006,6 +1008,135 @@ def parallax_u8(image_u8, depth_u16, poses, focus, fill, invert=False, want_mask
             if mask is not None:
                 mask[:, k0:k1].copy_(part_mask)
     return (out, mask) if want_mask else out
+
+
+# ---- autostereograms from depth (csrc/ds_autostereogram.hip; public interface: src/autostereogram_generation.py) ---------------------
+AUTOSTEREOGRAM_PERIODS = (16, 512)
+AUTOSTEREOGRAM_MAX_M = 128           # depth_factor = m / 256: at most 0.5
+AUTOSTEREOGRAM_MAX_TILE = 4096
+AUTOSTEREOGRAM_MODES = {'dots': 0, 'mono': 1}
+
+
+def autostereogram_separation(z, period, m):
+    """s(z) of ds_autostereogram_u8 (include/depthstereo.h): the on-screen separation in pixels of a point of nearness z (0..65535, an
+    integer or an integer array) at period P and depth factor m / 256, rounded half up, as int64.  s(0) = P; s never increases with z."""
+    z = np.asarray(z).astype(np.int64)
+    a = 256 * 65535
+    den = 2 * a - int(m) * z
+    return (4 * int(period) * (a - int(m) * z) + den) // (2 * den)
+
+
+def _autostereogram_pattern(pattern):
+    """'dots', 'mono', or the tile of a pattern as a C-contiguous uint8 array [ph,pw,3]; raises TypeError / ValueError."""
+    if isinstance(pattern, str):
+        if pattern not in AUTOSTEREOGRAM_MODES:
+            raise ValueError
+        return pattern
+    if isinstance(pattern, bytes) or pattern is None:
+        raise TypeError
+    if hasattr(pattern, 'convert') and hasattr(pattern, 'mode'):             # a PIL image: taken as its convert("RGB")
+        pattern = np.asarray(pattern.convert('RGB'), dtype=np.uint8)
+    tile = np.asarray(pattern)
+    if tile.dtype != np.uint8 or tile.ndim not in (2, 3) or (tile.ndim == 3 and tile.shape[2] not in (3, 4)):
+        raise TypeError
+    tile = np.repeat(tile[:, :, None], 3, axis=2) if tile.ndim == 2 else tile[:, :, :3]
+    if not (1 <= tile.shape[0] <= AUTOSTEREOGRAM_MAX_TILE and 1 <= tile.shape[1] <= AUTOSTEREOGRAM_MAX_TILE):
+        raise ValueError
+    return np.ascontiguousarray(tile)
+
+
+def autostereogram_params(p):
+    """(period, depth_factor), (..., pattern) or (..., pattern, seed) as (int period, int m, pattern, int seed), or ValueError.  period:
+    an integer in 16..512, the separation in pixels of the far plane (a bool is no integer).  depth_factor: a number mu, quantised as
+    m = rint(256 mu), which must land in 1..128 (a bool or a string is no number; a NaN is out of range).  pattern: 'dots' (coloured
+    random dots, the default), 'mono' (black / white dots), or an image -- a PIL image, taken as its convert("RGB"), or a uint8 array
+    [ph,pw], [ph,pw,3] or [ph,pw,4] with ph, pw in 1..4096 -- which comes back as a uint8 array [ph,pw,3].  seed: an integer in
+    0..2^32 - 1 (default 0).  Pure Python (the funnel checks its option with it before any device work)."""
+    usage = "(period, depth_factor[, pattern[, seed]])"
+    try:
+        if isinstance(p, (str, bytes)):
+            raise TypeError
+        q = tuple(p)
+        if len(q) not in (2, 3, 4):
+            raise TypeError
+    except TypeError:
+        raise ValueError("autostereogram must be %s, got %r" % (usage, p)) from None
+    try:
+        if isinstance(q[0], (str, bytes)):
+            raise TypeError
+        period, ok = _as_int(q[0])
+        if not (ok and AUTOSTEREOGRAM_PERIODS[0] <= period <= AUTOSTEREOGRAM_PERIODS[1]):
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("autostereogram: period must be an integer in %d..%d, got %r" % (AUTOSTEREOGRAM_PERIODS + (q[0],))) from None
+    try:
+        m = int(np.rint(256.0 * _as_float(q[1], 1.0)))
+        if not 1 <= m <= AUTOSTEREOGRAM_MAX_M:
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("autostereogram: depth_factor must be a number with rint(256 * depth_factor) in 1..%d, got %r"
+                         % (AUTOSTEREOGRAM_MAX_M, q[1])) from None
+    try:
+        pattern = _autostereogram_pattern(q[2]) if len(q) > 2 else 'dots'
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("autostereogram: pattern must be 'dots', 'mono', a PIL image or a uint8 array [ph,pw], [ph,pw,3] or [ph,pw,4] "
+                         "with ph, pw in 1..%d, got %r" % (AUTOSTEREOGRAM_MAX_TILE, q[2])) from None
+    try:
+        if len(q) > 3 and isinstance(q[3], (str, bytes)):
+            raise TypeError
+        seed, ok = _as_int(q[3]) if len(q) > 3 else (0, True)
+        if not (ok and 0 <= seed <= 0xFFFFFFFF):
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("autostereogram: seed must be an integer in 0..2^32 - 1, got %r" % (q[3],)) from None
+    return period, m, pattern, seed
+
+
+def autostereogram_u8(depth_u16, period, m, mode, seed, tile=None, invert=False, out=None):
+    """Autostereograms of uint16 depth maps [n,h,w] (cuda) -> uint8 [n,h,w,3] (ds_autostereogram_u8: the definition is in
+    include/depthstereo.h).  period 16..512; m 1..128 (the depth factor m / 256); mode 0 = coloured dots, 1 = black / white dots, 2 = the
+    pattern `tile`, a uint8 [ph,pw,3] with ph, pw in 1..4096: a cuda tensor on the depth's device, or a host array, which is uploaded;
+    seed 0..2^32 - 1; invert: black is near.  out: write into this contiguous uint8 cuda tensor [n,h,w,3].  One launch."""
+    torch = require_gpu()
+    try:
+        ok = not any(isinstance(v, (str, bytes)) for v in (period, m, mode, seed))
+        (period, ok_p), (m, ok_m), (mode, ok_k), (seed, ok_s) = _as_int(period), _as_int(m), _as_int(mode), _as_int(seed)
+        ok = (ok and ok_p and ok_m and ok_k and ok_s and AUTOSTEREOGRAM_PERIODS[0] <= period <= AUTOSTEREOGRAM_PERIODS[1]
+              and 1 <= m <= AUTOSTEREOGRAM_MAX_M and mode in (0, 1, 2) and 0 <= seed <= 0xFFFFFFFF)
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise DepthStereoError("autostereogram_u8: period must be an integer in %d..%d, m in 1..%d, mode 0, 1 or 2 and seed in 0..2^32 - 1, "
+                               "got %r, %r, %r, %r" % (AUTOSTEREOGRAM_PERIODS + (AUTOSTEREOGRAM_MAX_M, period, m, mode, seed)))
+    _check_depth_guide("autostereogram_u8", depth_u16)
+    depth_u16 = depth_u16.contiguous()
+    n, h, w = depth_u16.shape
+    if n == 0 or h == 0 or w == 0:
+        raise DepthStereoError("autostereogram_u8: empty depth %s" % (tuple(depth_u16.shape),))
+    dev = depth_u16.device
+    ph = pw = 0
+    tile_t = None
+    if mode == 2:
+        if isinstance(tile, np.ndarray) and tile.dtype == np.uint8:
+            tile_t = torch.from_numpy(np.array(tile, order='C')).to(dev)      # (a copy: the caller's array may be read-only)
+        elif torch.is_tensor(tile) and tile.dtype == torch.uint8 and tile.device == dev:
+            tile_t = tile.contiguous()
+        if (tile_t is None or tile_t.dim() != 3 or tile_t.shape[2] != 3 or not 1 <= tile_t.shape[0] <= AUTOSTEREOGRAM_MAX_TILE
+                or not 1 <= tile_t.shape[1] <= AUTOSTEREOGRAM_MAX_TILE):
+            raise DepthStereoError("autostereogram_u8: with mode 2 tile must be a uint8 array or cuda tensor (on the depth's device) [ph,pw,3] "
+                                   "with ph, pw in 1..%d, got %s %s" % (AUTOSTEREOGRAM_MAX_TILE, getattr(tile, "dtype", type(tile)),
+                                                                        tuple(getattr(tile, "shape", ()))))
+        ph, pw = int(tile_t.shape[0]), int(tile_t.shape[1])
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == dev and tuple(out.shape) == (n, h, w, 3)
+              and out.is_contiguous()):
+        raise DepthStereoError("autostereogram_u8: out must be a contiguous uint8 tensor %s on the depth's device" % ((n, h, w, 3),))
+    CALLS["ds_autostereogram_u8"] += 1
+    _check(lib().ds_autostereogram_u8(ctx_for(_dev_index(depth_u16)), depth_u16.data_ptr(), n, h, w, period, m, mode, seed,
+                                      tile_t.data_ptr() if tile_t is not None else None, ph, pw, 1 if invert else 0, out.data_ptr(),
+                                      _stream(depth_u16)))
+    return out
 
 
 # ---- video mode (csrc/ds_video.hip; host half: src/video_mode.py) ------------------------------------------------------------------

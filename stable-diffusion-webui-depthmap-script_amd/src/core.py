@@ -439,7 +439,8 @@ def _mark(g, name, stream=None):
 
 
 def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=None, normalmap_wrap=False, normalmap_bilateral=None,
-                  depth_refine=None, depth_refine_wrap=False, aomap=None, aomap_wrap=False, lensblur=None, parallax=None):
+                  depth_refine=None, depth_refine_wrap=False, aomap=None, aomap_wrap=False, lensblur=None, parallax=None,
+                  autostereogram=None):
     """Enqueue everything a group needs on the current stream -- H2D, network, post-processing, stereo, normal map, heat
     map, D2H into pinned buffers -- and return the handles; nothing here waits for the device except the post-processing
     branches that must know which predictions are flat (one sync per batch) and the percentile bisection of 'Outliers'."""
@@ -643,6 +644,9 @@ def _launch_group(gen, idxs, inputimages, inputdepthmaps, inp, device, stats=Non
                 pixels_t = upload_pixels("parallax_in", lambda im: np.asarray(im.convert("RGB"), dtype=np.uint8), rgb=images[0].mode == "RGB")
             from .parallax_generation import create_parallax_batch
             download(create_parallax_batch(pixels_t, d16, _native.parallax_poses(*parallax[:5]), parallax[5], parallax[6]), "parallax")
+        if autostereogram is not None:                                                               # ops['autostereogram'] (src/autostereogram_generation.py)
+            from .autostereogram_generation import create_autostereogram_batch
+            download(create_autostereogram_batch(d16, autostereogram[0], autostereogram[1] / 256.0, *autostereogram[2:]), "autostereogram")
         _mark(g, "per-pixel kernels done")
         ready = torch.cuda.Event()
         ready.record()                                        # everything the copies read has been enqueued (main or post stream)
@@ -841,6 +845,8 @@ def _unit_tasks(g, j):
         tasks.append(("lensblur", lambda: ('lensblur', _to_pil(host["lensblur"].numpy()[j]))))
     if "parallax" in host:                               # ops['parallax'] of this call: the frames of unit j, after 'lensblur', before the mesh
         tasks.append(("parallax", lambda: ('parallax', [_to_pil(f) for f in host["parallax"].numpy()[j]])))
+    if "autostereogram" in host:                         # ops['autostereogram'] of this call: after 'parallax', before the mesh
+        tasks.append(("autostereogram", lambda: ('autostereogram', _to_pil(host["autostereogram"].numpy()[j]))))
     return tasks
 
 
@@ -978,9 +984,16 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
     parallax = ops.get('parallax')
     if parallax is not None:
         parallax = _native.parallax_params(parallax)
+    # ops['autostereogram'] (not in the reference): (period, depth_factor[, pattern[, seed]]) = the single-image stereogram of the uint16
+    # depth map the stereo warp reads -- behind depth_refine, the refined one -- (src/autostereogram_generation.py), yielded as
+    # (i, 'autostereogram', image) after 'parallax'; the map is white = near, so invert stays off.  Absent / None = off, and then the
+    # call makes the launches, uploads and bytes it always made.  An option of THIS call, checked here before any device work.
+    autostereogram = ops.get('autostereogram')
+    if autostereogram is not None:
+        autostereogram = _native.autostereogram_params(autostereogram)
     model_holder.update_settings(**{k: v for k, v in ops.items()
                                     if k not in ('normalmap_wrap', 'normalmap_bilateral', 'depth_refine', 'depth_refine_wrap', 'aomap',
-                                                 'aomap_wrap', 'lensblur', 'parallax')})
+                                                 'aomap_wrap', 'lensblur', 'parallax', 'autostereogram')})
 
     torch = _native.require_gpu()        # the hot path has no CPU implementation, whatever COMPUTE_DEVICE says
     device = torch.device('cuda', torch.cuda.current_device())
@@ -1011,7 +1024,8 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
             try:
                 _t0 = _time.perf_counter()
                 launched, failure = _launch_group(gi & 1, idxs, inputimages, inputdepthmaps, inp, device, stats, normalmap_wrap,
-                                                  normalmap_bilateral, depth_refine, depth_refine_wrap, aomap, aomap_wrap, lensblur, parallax), None
+                                                  normalmap_bilateral, depth_refine, depth_refine_wrap, aomap, aomap_wrap, lensblur, parallax,
+                                                  autostereogram), None
                 stats["launch"] = stats.get("launch", 0.0) + (_time.perf_counter() - _t0)
             except Exception as e:          # noqa: BLE001 -- re-raised below, after the results that precede it
                 launched, failure = None, e
