@@ -454,6 +454,60 @@ int ds_autostereogram_rounds_u8(ds_ctx *ctx, const uint16_t *depth, int n, int h
                                 const uint8_t *tile, int ph, int pw, int invert, uint8_t *out, uint16_t *rounds, void *stream);
 
 /*
+ * ds_stereo_match_u8 -- depth from stereo pairs: the disparity map of the LEFT view of each of n row-aligned pairs by four-path
+ * semi-global matching (Hirschmueller 2008) on a 5x5 census, and from it a depth map, white = near.  The reference has no counterpart;
+ * this comment is the definition, and the only normative text.  Everything is an integer, and every step is min, +, a compare or an
+ * integer division, so the result does not depend on the order in which anything runs.  floor() below is the floor of the exact quotient.
+ * Inputs.  left, right [n,h,w,c] uint8, c in {1, 3, 4}, at any byte address.  The left image is the reference view.  Disparity delta means:
+ *   left column x shows what the right image shows at column x - delta; a larger delta is nearer.  D in {32, 64, 128}: the number of
+ *   disparities.  d0 in -128..127: the smallest one (negative: content in front of the screen plane); the candidates are delta = d0 + d,
+ *   d = 0..D-1.  P1 in 1..64, P2 in P1..255: the penalties of a disparity step of one and of more than one.  u in 0..50: the uniqueness
+ *   margin in percent.  lr in -1..3: the left-right tolerance, -1 = no check.
+ * 1. Luma.  Y = (77 R + 150 G + 29 B + 128) >> 8; with c = 1 the byte itself; with c = 4 the fourth channel is ignored.
+ * 2. Census, per image: 24 bits from the 5x5 window around a pixel, a bit set where the neighbour's Y is SMALLER than the centre's;
+ *    a neighbour outside the image is the nearest edge pixel.  Only Hamming distances are used: the bit order is the implementation's.
+ * 3. Cost.  C(y,x,d) = popcount(cl[y,x] ^ cr[y, x - (d0 + d)]) when that column lies in 0..w-1, else 24.
+ * 4. Paths, four directions r: left->right, right->left, top->bottom, bottom->top.  At the first pixel of a path L_r(p,.) = C(p,.);
+ *    afterwards, with q = p - r and m_r(q) = min_d L_r(q,d),
+ *      L_r(p,d) = C(p,d) + min(L_r(q,d), L_r(q,d-1) + P1, L_r(q,d+1) + P1, m_r(q) + P2) - m_r(q),
+ *    a d +- 1 outside 0..D-1 being absent.  S = sum_r L_r.  L_r <= 24 + 255 and S <= 1116: uint16 holds everything.
+ * 5. Winner.  d* = the SMALLEST d that minimises S(p,.), S1 its value.  The pixel fails uniqueness when some e with |e - d*| > 1 has
+ *    S(p,e) (100 - u) < S1 100.
+ * 6. Left-right check (lr >= 0).  dR(y,xr) = the smallest d minimising S(y, xr + d0 + d, d) over the d whose column xr + d0 + d lies in
+ *    the row; undefined when there is none.  With xr = x - (d0 + d*) the pixel fails when xr is outside the row, or dR(y,xr) is
+ *    undefined, or |dR(y,xr) - d*| > lr.
+ * 7. Sub-pixel.  For 0 < d* < D-1: a, b, c = S(d*-1), S(d*), S(d*+1), den = a + c - 2 b, frac = floor((16 (a - c) + den) / (2 den))
+ *    when den > 0, else 0.  (d* is the smallest minimiser, so a > b and den > 0 always: frac = floor(8 (a - c) / den + 1/2) with
+ *    -1 < (a - c) / den <= 1, so frac is in -8..8; c = b gives 8, a = b + 1 under a large c gives -8.)  At d* = 0 and
+ *    d* = D-1 frac = 0.  disp16 = 16 (d0 + d*) + frac, in 1/16 pixel.  valid = 1 for a pixel that passed 5 and 6, else 0.
+ * 8. Fill.  An invalid pixel takes the SMALLER of the nearest valid disp16 to its left and to its right in its own row (an occlusion
+ *    belongs to the background); with one side only, that side's; in a row without a valid pixel 16 d0.
+ * 9. Median.  disparity = the 3x3 median of the filled map, nearest-edge borders.
+ * 10. Depth.  Per image lo, hi = min, max of disparity; depth = floor(((v - lo) 131070 + (hi - lo)) / (2 (hi - lo))), and all zeros when
+ *    hi = lo.
+ * Outputs.  disparity [n,h,w] int16 (step 9).  valid [n,h,w] uint8, the mask of step 7, before the fill; may be NULL, at any byte
+ * address.  depth [n,h,w] uint16; may be NULL.  An image's result does not depend on its batch, on `group` or on the launch.
+ * Workspace.  ds_stereo_match_workspace_bytes(h, w, D) is one image's share -- the S volume (2 h w D bytes), two census planes, the filled
+ *   map, the lo / hi words, each rounded to 256 bytes -- and 0 for a size or a D the entry point refuses.  `workspace` holds `group`
+ *   shares (group in 1..n), 256-byte aligned, any content: images are processed `group` at a time, the workspace reused in stream order.
+ * DS_EINVAL, before any launch: a null pointer other than valid / depth; n, h or w <= 0; c, D, d0, P1, P2, u or lr out of range; group
+ * outside 1..n; workspace not 256-byte aligned, disparity or depth not 2-byte aligned.  Then DS_EUNSUPPORTED: h or w > 16384, n > 65535,
+ * or one image's workspace above 2 GiB (element offsets then stay inside 31 bits; byte offsets are size_t all the same).  Then DS_EINVAL:
+ * an output or the workspace overlapping an input or each other.  Asynchronous on `stream`, no allocation; per group five launches, six
+ * with depth (census, horizontal paths, vertical paths, winner + fill, median + min / max, depth).  No kernel-timer kind.
+ * The NumPy model is tests/stereo_match_cases.py.
+ * ds_stereo_match_stages_u8 is the same call restricted to the launches named by `stages`, a sum of 1 = census, 2 = horizontal paths,
+ * 4 = vertical paths, 8 = winner + fill, 16 = median, 32 = depth (1..63; 63 is ds_stereo_match_u8): tools/stereo_match_ab.py times each
+ * launch with it.  A partial run leaves partial results.
+ */
+size_t ds_stereo_match_workspace_bytes(int h, int w, int D);
+int ds_stereo_match_u8(ds_ctx *ctx, const uint8_t *left, const uint8_t *right, int n, int h, int w, int c, int D, int d0, int P1, int P2, int u,
+                       int lr, void *workspace, int group, int16_t *disparity, uint8_t *valid, uint16_t *depth, void *stream);
+int ds_stereo_match_stages_u8(ds_ctx *ctx, const uint8_t *left, const uint8_t *right, int n, int h, int w, int c, int D, int d0, int P1, int P2,
+                              int u, int lr, void *workspace, int group, int16_t *disparity, uint8_t *valid, uint16_t *depth, int stages,
+                              void *stream);
+
+/*
  * ds_frame_luma_hist -- per-frame luma histograms of a uint8 clip: the input of video mode's scene-cut detector (the reference
  * leaves cut detection as a TODO, src/video_mode.py:114, and has no implementation; this comment is the definition).
  * frames [n,h,w,c] uint8, dense, ANY byte alignment -> hist [n,256] uint32: hist[f][v] = the number of pixels of frame f with Y == v.

@@ -27,7 +27,7 @@ EXPORTS = [
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
-    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_aomap_u16", "ds_lensblur_u8", "ds_parallax_u8", "ds_autostereogram_u8", "ds_autostereogram_rounds_u8", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
+    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_aomap_u16", "ds_lensblur_u8", "ds_parallax_u8", "ds_autostereogram_u8", "ds_autostereogram_rounds_u8", "ds_stereo_match_workspace_bytes", "ds_stereo_match_u8", "ds_stereo_match_stages_u8", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
     "ds_preprocess_bicubic_rows", "ds_tokens_fixup", "ds_upsample_bicubic_to_f32", "ds_im2col3x3_s2_nhwc", "ds_dpt_head_front",
 ]
 
@@ -94,6 +94,10 @@ def lib():
             L.ds_parallax_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, ci, vp, vp, vp, vp]
             L.ds_autostereogram_u8.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ctypes.c_uint32, vp, ci, ci, ci, vp, vp]
             L.ds_autostereogram_rounds_u8.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ctypes.c_uint32, vp, ci, ci, ci, vp, vp, vp]
+            L.ds_stereo_match_workspace_bytes.argtypes = [ci, ci, ci]
+            L.ds_stereo_match_workspace_bytes.restype = ctypes.c_size_t
+            L.ds_stereo_match_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp]
+            L.ds_stereo_match_stages_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, ci, vp]
             L.ds_frame_luma_hist.argtypes =[vp, vp, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_smooth5_f32.argtypes = [vp, vp, ci, i64, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_joint_bilateral_u16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp]
@@ -1137,6 +1141,105 @@ def autostereogram_u8(depth_u16, period, m, mode, seed, tile=None, invert=False,
                                       tile_t.data_ptr() if tile_t is not None else None, ph, pw, 1 if invert else 0, out.data_ptr(),
                                       _stream(depth_u16)))
     return out
+
+
+# ---- depth from stereo pairs (csrc/ds_stereo_match.hip; public interface: src/stereo_matching.py) -----------------------------------
+STEREO_MATCH_DISPARITIES = (32, 64, 128)
+STEREO_MATCH_DEFAULTS = (64, 0, 4, 48, 5, 1)         # D, d0, P1, P2, u, lr
+STEREO_MATCH_WS_BYTES = 1 << 30                      # the workspace stereo_match_u8 allocates when the caller names no group
+STEREO_MATCH_MAX_SIDE = 16384
+
+
+def stereo_match_params(p):
+    """(D,), (D, d0), (D, d0, P1, P2), (D, d0, P1, P2, u) or (D, d0, P1, P2, u, lr) as six ints, or ValueError; what is left out takes
+    the defaults (64, 0, 4, 48, 5, 1).  D: 32, 64 or 128 disparities.  d0: the smallest disparity, an integer in -128..127.  P1 in 1..64
+    and P2 in P1..255: the penalties of semi-global matching.  u: the uniqueness margin in percent, 0..50.  lr: the left-right tolerance,
+    -1..3, -1 = no check.  All integers: a bool or a string is no number, and a NaN is out of range.  Pure Python (the funnel checks its
+    option with it before any device work)."""
+    usage = "(D[, d0[, P1, P2[, u[, lr]]]])"
+    try:
+        if isinstance(p, (str, bytes)):
+            raise TypeError
+        q = tuple(p)
+        if len(q) not in (1, 2, 4, 5, 6):
+            raise TypeError
+    except TypeError:
+        raise ValueError("stereo_match must be %s, got %r" % (usage, p)) from None
+    names = ("D", "d0", "P1", "P2", "u", "lr")
+    vals = list(STEREO_MATCH_DEFAULTS)
+    for k, v in enumerate(q):
+        try:
+            if isinstance(v, (str, bytes)):
+                raise TypeError
+            vals[k], ok = _as_int(v)
+            if not ok:
+                raise ValueError
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("stereo_match: %s must be an integer, got %r" % (names[k], v)) from None
+    D, d0, P1, P2, u, lr = vals
+    if D not in STEREO_MATCH_DISPARITIES:
+        raise ValueError("stereo_match: D must be one of %r, got %r" % (STEREO_MATCH_DISPARITIES, D))
+    if not -128 <= d0 <= 127:
+        raise ValueError("stereo_match: d0 must be in -128..127, got %r" % (d0,))
+    if not (1 <= P1 <= 64 and P1 <= P2 <= 255):
+        raise ValueError("stereo_match: P1 must be in 1..64 and P2 in P1..255, got %r, %r" % (P1, P2))
+    if not 0 <= u <= 50:
+        raise ValueError("stereo_match: u must be in 0..50, got %r" % (u,))
+    if not -1 <= lr <= 3:
+        raise ValueError("stereo_match: lr must be in -1..3, got %r" % (lr,))
+    return D, d0, P1, P2, u, lr
+
+
+def stereo_match_workspace_bytes(h, w, D):
+    """ds_stereo_match_workspace_bytes: one image's share of the workspace, 0 for a size or a D the entry point refuses."""
+    return int(lib().ds_stereo_match_workspace_bytes(int(h), int(w), int(D)))
+
+
+def stereo_match_u8(left, right, D, d0, P1, P2, u, lr, want_valid=False, want_depth=True, group=None):
+    """Disparity and depth of the left views of row-aligned stereo pairs: left, right uint8 cuda tensors [n,h,w,c], c in {1, 3, 4}, same
+    shape and device (ds_stereo_match_u8: the definition is in include/depthstereo.h).  Returns (disparity int16 [n,h,w] in 1/16 pixel,
+    valid uint8 [n,h,w] or None, depth uint16 [n,h,w] or None) on that device.  The workspace comes from torch's allocator and holds
+    `group` images; group=None picks the largest group whose workspace stays within STEREO_MATCH_WS_BYTES (1 GiB), and at least 1.  The
+    result does not depend on the group."""
+    torch = require_gpu()
+    try:
+        D, d0, P1, P2, u, lr = stereo_match_params((D, d0, P1, P2, u, lr))
+    except ValueError as e:
+        raise DepthStereoError("stereo_match_u8: %s" % (e,)) from None
+    for name, t in (("left", left), ("right", right)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 4 and t.shape[3] in (1, 3, 4)):
+            raise DepthStereoError("stereo_match_u8: %s must be a uint8 cuda tensor [n,h,w,c] with c in {1, 3, 4}, got %s %s"
+                                   % (name, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    if tuple(left.shape) != tuple(right.shape) or left.device != right.device:
+        raise DepthStereoError("stereo_match_u8: left %s and right %s must have one shape and one device"
+                               % (tuple(left.shape), tuple(right.shape)))
+    n, h, w, c = left.shape
+    if n == 0 or h == 0 or w == 0:
+        raise DepthStereoError("stereo_match_u8: empty images %s" % (tuple(left.shape),))
+    per_image = stereo_match_workspace_bytes(h, w, D) if max(h, w) <= STEREO_MATCH_MAX_SIDE and n <= 65535 else 0
+    if per_image == 0 or per_image > 1 << 31:
+        raise DepthStereoError("stereo_match_u8: n must be <= 65535, h and w <= %d and one image's workspace <= 2 GiB, got %s at D = %d"
+                               % (STEREO_MATCH_MAX_SIDE, tuple(left.shape), D))
+    if group is None:
+        group = max(1, min(n, STEREO_MATCH_WS_BYTES // per_image))
+    else:
+        try:
+            group, ok = _as_int(group)
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not (ok and 1 <= group <= n):
+            raise DepthStereoError("stereo_match_u8: group must be an integer in 1..n = %d, got %r" % (n, group))
+    left, right = left.contiguous(), right.contiguous()
+    dev = left.device
+    disparity = torch.empty((n, h, w), dtype=torch.int16, device=dev)
+    valid = torch.empty((n, h, w), dtype=torch.uint8, device=dev) if want_valid else None
+    depth = torch.empty((n, h, w), dtype=torch.uint16, device=dev) if want_depth else None
+    workspace = torch.empty((group * per_image,), dtype=torch.uint8, device=dev)          # (torch's blocks are 512-byte aligned)
+    CALLS["ds_stereo_match_u8"] += 1
+    _check(lib().ds_stereo_match_u8(ctx_for(_dev_index(left)), left.data_ptr(), right.data_ptr(), n, h, w, c, D, d0, P1, P2, u, lr,
+                                    workspace.data_ptr(), group, disparity.data_ptr(), valid.data_ptr() if valid is not None else None,
+                                    depth.data_ptr() if depth is not None else None, _stream(left)))
+    return disparity, valid, depth
 
 
 # ---- video mode (csrc/ds_video.hip; host half: src/video_mode.py) ------------------------------------------------------------------

@@ -991,9 +991,25 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
     autostereogram = ops.get('autostereogram')
     if autostereogram is not None:
         autostereogram = _native.autostereogram_params(autostereogram)
+    # ops['stereo_input'] (not in the reference): (layout[, D[, d0[, P1, P2[, u[, lr]]]]]) = every input image is a stereo pair in that
+    # layout ('left-right', 'right-left', 'top-bottom', 'bottom-top').  Before anything else the call splits it and computes the depth
+    # map of the LEFT view by semi-global matching (src/stereo_matching.py); from there on it is the call the caller would have made
+    # with the left halves as inputimages and those maps as inputdepthmaps, so depth_refine and every product apply and no network is
+    # loaded.  Absent / None = off, and then the call makes the launches, uploads and bytes it always made.  An option of THIS call,
+    # checked here before any device work; together with inputdepthmaps it is a ValueError.
+    stereo_input = ops.get('stereo_input')
+    if stereo_input is not None:
+        from . import stereo_matching
+        stereo_input = stereo_matching.stereo_input_params(stereo_input)
+        if any(x is not None for x in inputdepthmaps):
+            raise ValueError("ops['stereo_input'] computes the depth maps from the pairs: inputdepthmaps must be empty with it")
+        pairs = [stereo_matching.split_stereo_pair(image, stereo_input[0]) for image in inputimages]
+        inputimages = [left for left, _ in pairs]
+        inputdepthmaps = [stereo_matching.depth_from_stereo(left, right, *stereo_input[1:]) for left, right in pairs]
+        inputdepthmaps_complete = True
     model_holder.update_settings(**{k: v for k, v in ops.items()
                                     if k not in ('normalmap_wrap', 'normalmap_bilateral', 'depth_refine', 'depth_refine_wrap', 'aomap',
-                                                 'aomap_wrap', 'lensblur', 'parallax', 'autostereogram')})
+                                                 'aomap_wrap', 'lensblur', 'parallax', 'autostereogram', 'stereo_input')})
 
     torch = _native.require_gpu()        # the hot path has no CPU implementation, whatever COMPUTE_DEVICE says
     device = torch.device('cuda', torch.cuda.current_device())
