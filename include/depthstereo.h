@@ -508,6 +508,64 @@ int ds_stereo_match_stages_u8(ds_ctx *ctx, const uint8_t *left, const uint8_t *r
                               void *stream);
 
 /*
+ * ds_stereo_match_ex_u8 -- ds_stereo_match_u8 with eight paths and a speckle filter.  The definition is that of ds_stereo_match_u8,
+ * steps 1-10 of the comment above, with three more parameters and two extended steps; this comment and that one are the normative text.
+ * paths in {4, 8}.  With 8, step 4 has four more directions r = (dy, dx): (+1,+1), (-1,-1), (+1,-1), (-1,+1).  The recurrence, P1, P2,
+ *   the absent d +- 1 and "at the first pixel of a path L_r = C" are unchanged; the first pixel of a path is the one whose predecessor
+ *   p - r lies outside the image, so in an image of one row or one column every diagonal path has length 1 and L_r = C there.  S is the
+ *   sum over all eight directions: L_r <= 24 + 255 = 279, S <= 8 * 279 = 2232, uint16 holds it, and S (100 - u) <= 223200 fits an int32.
+ *   Steps 5-7 read the new S unchanged: den = a + c - 2 b <= 2 * 2232, and frac stays in -8..8 by the argument of step 7, which uses
+ *   a > b, c >= b and nothing else.
+ * speckle_size in 0..65535, 0 = off; speckle_range in 0..16 pixels.  With speckle_size > 0 a step 7b runs between steps 7 and 8: the
+ *   speckle filter below on (disp16, valid) of step 7 with size = speckle_size and t = 16 speckle_range.  The `valid` output and the
+ *   fill of step 8 use the mask AFTER 7b (with speckle_size = 0: the mask of step 7, as before).
+ * With paths = 4 and speckle_size = 0 every output equals ds_stereo_match_u8's bit for bit.
+ * ds_stereo_match_ex_workspace_bytes(h, w, D, paths, speckle_size) is one image's share: ds_stereo_match_workspace_bytes(h, w, D) and,
+ *   with speckle_size > 0, behind it disp16 (2 h w bytes), the masks of steps 7 and 7b (h w each), the links and the counters of the
+ *   filter (4 h w each), each rounded to 256 bytes; 0 for whatever the entry point refuses.  `workspace` holds `group` shares, 256-byte
+ *   aligned, any content.
+ * Refusals, before any launch, as ds_stereo_match_u8's and in its order, the entry point naming itself in ds_last_error(): DS_EINVAL for
+ *   a null pointer other than valid / depth, n, h or w <= 0, c, D, d0, P1, P2, u, lr, paths, speckle_size or speckle_range out of range,
+ *   group outside 1..n, misalignment; then DS_EUNSUPPORTED for h or w > 16384, n > 65535 or a share above 2 GiB; then DS_EINVAL for an
+ *   output or the workspace overlapping an input or each other.  Asynchronous on `stream`, no allocation.  Launches per group: those of
+ *   ds_stereo_match_u8; with paths = 8 two more behind the vertical paths, one per diagonal orientation (each S element lies on exactly
+ *   one line of an orientation, so a launch never shares an element between lines; stream order hands S from launch to launch); with
+ *   speckle_size > 0 the winner launch stops before its fill and leaves disp16 and valid in the workspace, the filter's four launches
+ *   follow, then one row-fill launch: 5 (6 with depth) + 2 + 5.  No kernel-timer kind.
+ * ds_stereo_match_ex_stages_u8 is the same call restricted to the launches named by `stages` (1..255): the bits of
+ *   ds_stereo_match_stages_u8, 64 = the two diagonal launches, 128 = the speckle filter and the fill behind it; a bit whose launches the
+ *   parameters switch off does nothing.  tools/stereo_match_ex_ab.py times with it.  A partial run leaves partial results.
+ * The NumPy model is tests/stereo_match_ex_cases.py.
+ *
+ * ds_speckle_filter_i16 -- step 7b as an entry point of its own: rejects small connected regions of similar disparity.
+ * disp [n,h,w] int16, valid [n,h,w] uint8 (any byte address), size in 1..65535, t in 0..65535.  Per image: the nodes are the pixels with
+ *   valid != 0.  Two 4-neighbours are linked exactly when both are nodes and |disp(p) - disp(q)| <= t, the difference taken in int32
+ *   (-32768 beside 32767 differ by 65535).  No link crosses an image border or joins two images.  A component is a connected component
+ *   of that graph; links are not transitive in value: a ramp in steps of t is one component.
+ * size_out [n,h,w] uint32 (may be NULL; 4-byte aligned): the pixel count of the pixel's component, 0 for a non-node.
+ * valid_out [n,h,w] uint8 (any byte address; may not alias valid): 1 for a node whose component has MORE than `size` pixels, else 0.
+ *   Membership and counts are properties of the graph: no schedule can change a bit.
+ * ds_speckle_filter_workspace_bytes(h, w) is one image's share: links and counters, 4 h w bytes each, each rounded to 256; 0 for a
+ *   refused shape.  `workspace` holds `group` shares (group in 1..n), 256-byte aligned, any content: the first launch writes every link
+ *   and counter before any launch reads one.
+ * DS_EINVAL, before any launch: a null pointer other than size_out; n, h or w <= 0; size or t out of range; group outside 1..n; workspace
+ *   not 256-byte aligned, disp not 2-byte or size_out not 4-byte aligned.  Then DS_EUNSUPPORTED: h or w > 16384, n > 65535, or a share
+ *   above 2 GiB (h w <= 2^28: pixel indices are int32).  Then DS_EINVAL: valid_out, size_out or the workspace overlapping an input or each
+ *   other.  Asynchronous on `stream`, no allocation; four launches per group (links, merge, roots + counts, outputs); no kernel waits
+ *   for another workgroup.  The model is the flood fill of tests/stereo_match_ex_cases.py.
+ */
+size_t ds_stereo_match_ex_workspace_bytes(int h, int w, int D, int paths, int speckle_size);
+int ds_stereo_match_ex_u8(ds_ctx *ctx, const uint8_t *left, const uint8_t *right, int n, int h, int w, int c, int D, int d0, int P1, int P2,
+                          int u, int lr, int paths, int speckle_size, int speckle_range, void *workspace, int group, int16_t *disparity,
+                          uint8_t *valid, uint16_t *depth, void *stream);
+int ds_stereo_match_ex_stages_u8(ds_ctx *ctx, const uint8_t *left, const uint8_t *right, int n, int h, int w, int c, int D, int d0, int P1,
+                                 int P2, int u, int lr, int paths, int speckle_size, int speckle_range, void *workspace, int group,
+                                 int16_t *disparity, uint8_t *valid, uint16_t *depth, int stages, void *stream);
+size_t ds_speckle_filter_workspace_bytes(int h, int w);
+int ds_speckle_filter_i16(ds_ctx *ctx, const int16_t *disp, const uint8_t *valid, int n, int h, int w, int size, int t, void *workspace,
+                          int group, uint8_t *valid_out, uint32_t *size_out, void *stream);
+
+/*
  * ds_frame_luma_hist -- per-frame luma histograms of a uint8 clip: the input of video mode's scene-cut detector (the reference
  * leaves cut detection as a TODO, src/video_mode.py:114, and has no implementation; this comment is the definition).
  * frames [n,h,w,c] uint8, dense, ANY byte alignment -> hist [n,256] uint32: hist[f][v] = the number of pixels of frame f with Y == v.

@@ -27,7 +27,7 @@ EXPORTS = [
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
-    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_aomap_u16", "ds_lensblur_u8", "ds_parallax_u8", "ds_autostereogram_u8", "ds_autostereogram_rounds_u8", "ds_stereo_match_workspace_bytes", "ds_stereo_match_u8", "ds_stereo_match_stages_u8", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
+    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_aomap_u16", "ds_lensblur_u8", "ds_parallax_u8", "ds_autostereogram_u8", "ds_autostereogram_rounds_u8", "ds_stereo_match_workspace_bytes", "ds_stereo_match_u8", "ds_stereo_match_stages_u8", "ds_stereo_match_ex_workspace_bytes", "ds_stereo_match_ex_u8", "ds_stereo_match_ex_stages_u8", "ds_speckle_filter_workspace_bytes", "ds_speckle_filter_i16", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
     "ds_preprocess_bicubic_rows", "ds_tokens_fixup", "ds_upsample_bicubic_to_f32", "ds_im2col3x3_s2_nhwc", "ds_dpt_head_front",
 ]
 
@@ -98,6 +98,13 @@ def lib():
             L.ds_stereo_match_workspace_bytes.restype = ctypes.c_size_t
             L.ds_stereo_match_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp]
             L.ds_stereo_match_stages_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, ci, vp]
+            L.ds_stereo_match_ex_workspace_bytes.argtypes = [ci, ci, ci, ci, ci]
+            L.ds_stereo_match_ex_workspace_bytes.restype = ctypes.c_size_t
+            L.ds_stereo_match_ex_u8.argtypes = [vp, vp, vp] + [ci] * 13 + [vp, ci, vp, vp, vp, vp]
+            L.ds_stereo_match_ex_stages_u8.argtypes = [vp, vp, vp] + [ci] * 13 + [vp, ci, vp, vp, vp, ci, vp]
+            L.ds_speckle_filter_workspace_bytes.argtypes = [ci, ci]
+            L.ds_speckle_filter_workspace_bytes.restype = ctypes.c_size_t
+            L.ds_speckle_filter_i16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, ci, vp, vp, vp]
             L.ds_frame_luma_hist.argtypes =[vp, vp, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_smooth5_f32.argtypes = [vp, vp, ci, i64, ci, ci, ci, ci, vp, vp]
             L.ds_temporal_joint_bilateral_u16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp]
@@ -1240,6 +1247,145 @@ def stereo_match_u8(left, right, D, d0, P1, P2, u, lr, want_valid=False, want_de
                                     workspace.data_ptr(), group, disparity.data_ptr(), valid.data_ptr() if valid is not None else None,
                                     depth.data_ptr() if depth is not None else None, _stream(left)))
     return disparity, valid, depth
+
+
+STEREO_MATCH_EX_DEFAULTS = (4, 0, 0)                 # paths, speckle_size, speckle_range: ds_stereo_match_u8
+STEREO_MATCH_EX_PRESET = (8, 64, 1)                  # a starting point for stereo photos, not a measured optimum
+
+
+def stereo_match_ex_params(p):
+    """(paths, speckle_size, speckle_range) of ds_stereo_match_ex_u8 as three ints, or ValueError.  paths: 4 or 8.  speckle_size: 0..65535
+    pixels, 0 = no speckle filter.  speckle_range: 0..16 pixels of disparity.  All integers: a bool or a string is no number, and a NaN is
+    out of range.  Pure Python (the funnel checks its options with it before any device work)."""
+    try:
+        if isinstance(p, (str, bytes)):
+            raise TypeError
+        q = tuple(p)
+        if len(q) != 3:
+            raise TypeError
+    except TypeError:
+        raise ValueError("stereo_match_ex must be (paths, speckle_size, speckle_range), got %r" % (p,)) from None
+    names = ("paths", "speckle_size", "speckle_range")
+    vals = [0, 0, 0]
+    for k, v in enumerate(q):
+        try:
+            if isinstance(v, (str, bytes)):
+                raise TypeError
+            vals[k], ok = _as_int(v)
+            if not ok:
+                raise ValueError
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("stereo_match_ex: %s must be an integer, got %r" % (names[k], v)) from None
+    paths, size, rng = vals
+    if paths not in (4, 8):
+        raise ValueError("stereo_match_ex: paths must be 4 or 8, got %r" % (paths,))
+    if not 0 <= size <= 65535:
+        raise ValueError("stereo_match_ex: speckle_size must be in 0..65535, got %r" % (size,))
+    if not 0 <= rng <= 16:
+        raise ValueError("stereo_match_ex: speckle_range must be in 0..16, got %r" % (rng,))
+    return paths, size, rng
+
+
+def stereo_match_ex_workspace_bytes(h, w, D, paths, speckle_size):
+    """ds_stereo_match_ex_workspace_bytes: one image's share of the workspace, 0 for what the entry point refuses."""
+    return int(lib().ds_stereo_match_ex_workspace_bytes(int(h), int(w), int(D), int(paths), int(speckle_size)))
+
+
+def speckle_filter_workspace_bytes(h, w):
+    """ds_speckle_filter_workspace_bytes: one image's share of the workspace, 0 for a shape the entry point refuses."""
+    return int(lib().ds_speckle_filter_workspace_bytes(int(h), int(w)))
+
+
+def _stereo_group(who, group, n, per_image):
+    if group is None:
+        return max(1, min(n, STEREO_MATCH_WS_BYTES // per_image))
+    try:
+        group, ok = _as_int(group)
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not (ok and 1 <= group <= n):
+        raise DepthStereoError("%s: group must be an integer in 1..n = %d, got %r" % (who, n, group))
+    return group
+
+
+def stereo_match_ex_u8(left, right, D, d0, P1, P2, u, lr, paths, speckle_size, speckle_range, want_valid=False, want_depth=True, group=None):
+    """stereo_match_u8 with eight paths and a speckle filter (ds_stereo_match_ex_u8: the definition is in include/depthstereo.h): paths 4
+    or 8; speckle_size 0..65535, 0 = off; speckle_range 0..16 pixels.  The same inputs, outputs, workspace rule and group as
+    stereo_match_u8; `valid` is the mask behind the speckle filter.  With (4, 0, r) the outputs are stereo_match_u8's bit for bit."""
+    torch = require_gpu()
+    try:
+        D, d0, P1, P2, u, lr = stereo_match_params((D, d0, P1, P2, u, lr))
+        paths, speckle_size, speckle_range = stereo_match_ex_params((paths, speckle_size, speckle_range))
+    except ValueError as e:
+        raise DepthStereoError("stereo_match_ex_u8: %s" % (e,)) from None
+    for name, t in (("left", left), ("right", right)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 4 and t.shape[3] in (1, 3, 4)):
+            raise DepthStereoError("stereo_match_ex_u8: %s must be a uint8 cuda tensor [n,h,w,c] with c in {1, 3, 4}, got %s %s"
+                                   % (name, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    if tuple(left.shape) != tuple(right.shape) or left.device != right.device:
+        raise DepthStereoError("stereo_match_ex_u8: left %s and right %s must have one shape and one device"
+                               % (tuple(left.shape), tuple(right.shape)))
+    n, h, w, c = left.shape
+    if n == 0 or h == 0 or w == 0:
+        raise DepthStereoError("stereo_match_ex_u8: empty images %s" % (tuple(left.shape),))
+    per_image = stereo_match_ex_workspace_bytes(h, w, D, paths, speckle_size) if max(h, w) <= STEREO_MATCH_MAX_SIDE and n <= 65535 else 0
+    if per_image == 0 or per_image > 1 << 31:
+        raise DepthStereoError("stereo_match_ex_u8: n must be <= 65535, h and w <= %d and one image's workspace <= 2 GiB, got %s at D = %d"
+                               % (STEREO_MATCH_MAX_SIDE, tuple(left.shape), D))
+    group = _stereo_group("stereo_match_ex_u8", group, n, per_image)
+    left, right = left.contiguous(), right.contiguous()
+    dev = left.device
+    disparity = torch.empty((n, h, w), dtype=torch.int16, device=dev)
+    valid = torch.empty((n, h, w), dtype=torch.uint8, device=dev) if want_valid else None
+    depth = torch.empty((n, h, w), dtype=torch.uint16, device=dev) if want_depth else None
+    workspace = torch.empty((group * per_image,), dtype=torch.uint8, device=dev)          # (torch's blocks are 512-byte aligned)
+    CALLS["ds_stereo_match_ex_u8"] += 1
+    _check(lib().ds_stereo_match_ex_u8(ctx_for(_dev_index(left)), left.data_ptr(), right.data_ptr(), n, h, w, c, D, d0, P1, P2, u, lr, paths,
+                                       speckle_size, speckle_range, workspace.data_ptr(), group, disparity.data_ptr(),
+                                       valid.data_ptr() if valid is not None else None, depth.data_ptr() if depth is not None else None,
+                                       _stream(left)))
+    return disparity, valid, depth
+
+
+def speckle_filter_i16(disp, valid, size, t, want_sizes=False, group=None):
+    """The speckle filter (ds_speckle_filter_i16: the definition is in include/depthstereo.h): disp int16 and valid uint8 cuda tensors
+    [n,h,w] on one device; size 1..65535 pixels; t 0..65535 in disp's units.  Returns (valid_out uint8 [n,h,w], size_out int32 [n,h,w]
+    or None): valid_out is 1 where a valid pixel's component -- 4-neighbours whose values differ by at most t -- has more than `size`
+    pixels; size_out holds the component's pixel count (its bits are the uint32 counts, which stay below 2^28), 0 for an invalid
+    pixel.  The workspace comes from torch's allocator, as stereo_match_u8's does."""
+    torch = require_gpu()
+    try:
+        if isinstance(size, (str, bytes)) or isinstance(t, (str, bytes)):
+            raise TypeError
+        (size, ok_s), (t, ok_t) = _as_int(size), _as_int(t)
+        if not (ok_s and ok_t and 1 <= size <= 65535 and 0 <= t <= 65535):
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise DepthStereoError("speckle_filter_i16: size must be an integer in 1..65535 and t one in 0..65535, got %r, %r" % (size, t)) from None
+    for name, x, dt in (("disp", disp, torch.int16), ("valid", valid, torch.uint8)):
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == dt and x.dim() == 3):
+            raise DepthStereoError("speckle_filter_i16: %s must be a %s cuda tensor [n,h,w], got %s %s"
+                                   % (name, dt, getattr(x, "dtype", type(x)), tuple(getattr(x, "shape", ()))))
+    if tuple(disp.shape) != tuple(valid.shape) or disp.device != valid.device:
+        raise DepthStereoError("speckle_filter_i16: disp %s and valid %s must have one shape and one device"
+                               % (tuple(disp.shape), tuple(valid.shape)))
+    n, h, w = disp.shape
+    if n == 0 or h == 0 or w == 0:
+        raise DepthStereoError("speckle_filter_i16: empty maps %s" % (tuple(disp.shape),))
+    per_image = speckle_filter_workspace_bytes(h, w) if max(h, w) <= STEREO_MATCH_MAX_SIDE and n <= 65535 else 0
+    if per_image == 0 or per_image > 1 << 31:
+        raise DepthStereoError("speckle_filter_i16: n must be <= 65535, h and w <= %d and h w <= 2^28, got %s"
+                               % (STEREO_MATCH_MAX_SIDE, tuple(disp.shape)))
+    group = _stereo_group("speckle_filter_i16", group, n, per_image)
+    disp, valid = disp.contiguous(), valid.contiguous()
+    dev = disp.device
+    valid_out = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
+    size_out = torch.empty((n, h, w), dtype=torch.int32, device=dev) if want_sizes else None
+    workspace = torch.empty((group * per_image,), dtype=torch.uint8, device=dev)
+    CALLS["ds_speckle_filter_i16"] += 1
+    _check(lib().ds_speckle_filter_i16(ctx_for(_dev_index(disp)), disp.data_ptr(), valid.data_ptr(), n, h, w, size, t, workspace.data_ptr(),
+                                       group, valid_out.data_ptr(), size_out.data_ptr() if size_out is not None else None, _stream(disp)))
+    return valid_out, size_out
 
 
 # ---- video mode (csrc/ds_video.hip; host half: src/video_mode.py) ------------------------------------------------------------------

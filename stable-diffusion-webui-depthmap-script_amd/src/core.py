@@ -996,20 +996,28 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
     # map of the LEFT view by semi-global matching (src/stereo_matching.py); from there on it is the call the caller would have made
     # with the left halves as inputimages and those maps as inputdepthmaps, so depth_refine and every product apply and no network is
     # loaded.  Absent / None = off, and then the call makes the launches, uploads and bytes it always made.  An option of THIS call,
-    # checked here before any device work; together with inputdepthmaps it is a ValueError.
+    # checked here before any device work; together with inputdepthmaps it is a ValueError.  Beside it, and only beside it,
+    # ops['stereo_paths']: 4 | 8 (8 adds the diagonal paths) and ops['stereo_speckle']: (size, range), the speckle filter between the
+    # checks and the fill (ds_stereo_match_ex_u8); absent, the matching is ds_stereo_match_u8's, launch for launch.
     stereo_input = ops.get('stereo_input')
     if stereo_input is not None:
         from . import stereo_matching
         stereo_input = stereo_matching.stereo_input_params(stereo_input)
+        stereo_ex = stereo_matching._ex_params(4 if ops.get('stereo_paths') is None else ops['stereo_paths'], ops.get('stereo_speckle'),
+                                               "ops['stereo_paths'] / ops['stereo_speckle']")
         if any(x is not None for x in inputdepthmaps):
             raise ValueError("ops['stereo_input'] computes the depth maps from the pairs: inputdepthmaps must be empty with it")
         pairs = [stereo_matching.split_stereo_pair(image, stereo_input[0]) for image in inputimages]
         inputimages = [left for left, _ in pairs]
-        inputdepthmaps = [stereo_matching.depth_from_stereo(left, right, *stereo_input[1:]) for left, right in pairs]
+        inputdepthmaps = [stereo_matching.depth_from_stereo(left, right, *stereo_input[1:], paths=stereo_ex[0],
+                                                            speckle=stereo_ex[1:] if stereo_ex[1] else None) for left, right in pairs]
         inputdepthmaps_complete = True
+    elif ops.get('stereo_paths') is not None or ops.get('stereo_speckle') is not None:
+        raise ValueError("ops['stereo_paths'] and ops['stereo_speckle'] are options of ops['stereo_input'] and need it")
     model_holder.update_settings(**{k: v for k, v in ops.items()
                                     if k not in ('normalmap_wrap', 'normalmap_bilateral', 'depth_refine', 'depth_refine_wrap', 'aomap',
-                                                 'aomap_wrap', 'lensblur', 'parallax', 'autostereogram', 'stereo_input')})
+                                                 'aomap_wrap', 'lensblur', 'parallax', 'autostereogram', 'stereo_input', 'stereo_paths',
+                                                 'stereo_speckle')})
 
     torch = _native.require_gpu()        # the hot path has no CPU implementation, whatever COMPUTE_DEVICE says
     device = torch.device('cuda', torch.cuda.current_device())

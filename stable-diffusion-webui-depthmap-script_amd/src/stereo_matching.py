@@ -16,7 +16,12 @@ plane.  Disparity d means: left column x shows what the right image shows at col
 percent, lr_check -1..3 pixels (-1: off).  The defaults (64, 0, 4, 48, 5, 1) are libSGM's 10 / 120 scaled from a 62-bit to a 24-bit
 census: starting points, not measured optima.  Pairs are taken as rectified (row-aligned), as SBS material is.
 
-In the funnel: core_generation_funnel(..., ops={'stereo_input': (layout[, D[, d0[, P1, P2[, u[, lr]]]]])}).
+paths=8 adds the four diagonal directions and speckle=(size, range) a speckle filter between the checks and the fill
+(ds_stereo_match_ex_u8); paths=8, speckle=(64, 1) is a starting point for stereo photos, not a measured optimum.  filter_speckles is the
+filter alone, for a disparity map of the caller's.
+
+In the funnel: core_generation_funnel(..., ops={'stereo_input': (layout[, D[, d0[, P1, P2[, u[, lr]]]]])}), and beside it
+'stereo_paths': 4 | 8 and 'stereo_speckle': (size, range).
 """
 import numpy as np
 from PIL import Image
@@ -88,27 +93,86 @@ def _params(max_disparity, min_disparity, p1, p2, uniqueness, lr_check, who):
         raise _native.DepthStereoError('%s: %s' % (who, e)) from None
 
 
-def depth_from_stereo(left, right, max_disparity=64, min_disparity=0, p1=4, p2=48, uniqueness=5, lr_check=1, return_disparity=False):
+def _ex_params(paths, speckle, who):
+    """(paths, speckle) as (paths, speckle_size, speckle_range), or ValueError.  speckle: None or (size, range); size 0 is off too."""
+    if speckle is None:
+        size, rng = 0, 0
+    else:
+        try:
+            if isinstance(speckle, (str, bytes)):
+                raise TypeError
+            size, rng = tuple(speckle)
+        except (TypeError, ValueError):
+            raise ValueError("%s: speckle must be None or (size, range), got %r" % (who, speckle)) from None
+    try:
+        return _native.stereo_match_ex_params((paths, size, rng))
+    except ValueError as e:
+        raise ValueError("%s: %s" % (who, e)) from None
+
+
+def _ex_check(paths, speckle, who):
+    try:
+        return _ex_params(paths, speckle, who)
+    except ValueError as e:
+        raise _native.DepthStereoError(str(e)) from None
+
+
+def _match(left, right, params, paths, speckle, who, **kwargs):
+    """ds_stereo_match_u8 with the defaults of paths and speckle, ds_stereo_match_ex_u8 otherwise."""
+    ex = _ex_check(paths, speckle, who)
+    if ex[0] == 4 and ex[1] == 0:
+        return _native.stereo_match_u8(left, right, *params, **kwargs)
+    return _native.stereo_match_ex_u8(left, right, *params, *ex, **kwargs)
+
+
+def depth_from_stereo(left, right, max_disparity=64, min_disparity=0, p1=4, p2=48, uniqueness=5, lr_check=1, return_disparity=False,
+                      paths=4, speckle=None):
     """left, right: PIL images or uint8 arrays of one size and channel count.  Returns the depth map of the left view as a PIL 'I;16'
     image, white = near; with return_disparity also the disparity in pixels (float32 [h,w], exact sixteenths) and the bool mask of the
     pixels that passed the uniqueness and left-right checks (the others were filled from their row).  A bad input or parameter raises
-    DepthStereoError before any launch."""
+    DepthStereoError before any launch.  paths: 4 or 8 aggregation directions (8 adds the diagonals: fewer streaks on slanted
+    silhouettes and weak texture).  speckle: None or (size, range) -- connected regions of at most `size` pixels whose neighbouring
+    disparities differ by at most `range` pixels are rejected before the fill.  With the defaults the call is ds_stereo_match_u8's;
+    paths=8, speckle=(64, 1) is a starting point for stereo photos, not a measured optimum."""
     params = _params(max_disparity, min_disparity, p1, p2, uniqueness, lr_check, 'depth_from_stereo')
+    _ex_check(paths, speckle, 'depth_from_stereo')
     a, b = _pixels(left, 'depth_from_stereo', 'left'), _pixels(right, 'depth_from_stereo', 'right')
     if a.shape != b.shape:
         raise _native.DepthStereoError('depth_from_stereo: left %s and right %s must have one shape' % (a.shape, b.shape))
     torch = _native.require_gpu()
     dev = torch.device('cuda', torch.cuda.current_device())
-    disparity, valid, depth = _native.stereo_match_u8(torch.from_numpy(a).to(dev).unsqueeze(0), torch.from_numpy(b).to(dev).unsqueeze(0),
-                                                      *params, want_valid=bool(return_disparity))
+    disparity, valid, depth = _match(torch.from_numpy(a).to(dev).unsqueeze(0), torch.from_numpy(b).to(dev).unsqueeze(0), params, paths,
+                                     speckle, 'depth_from_stereo', want_valid=bool(return_disparity))
     image = Image.fromarray(depth[0].cpu().numpy())                          # uint16 [h,w]: mode 'I;16'
     if not return_disparity:
         return image
     return image, disparity[0].cpu().numpy().astype(np.float32) / np.float32(16.0), valid[0].cpu().numpy().astype(bool)
 
 
-def depth_from_stereo_batch(left_u8, right_u8, max_disparity=64, min_disparity=0, p1=4, p2=48, uniqueness=5, lr_check=1):
-    """left_u8, right_u8 [n,h,w,c] uint8 cuda tensors -> uint16 [n,h,w] on that device: one ds_stereo_match_u8 call.  Images of a batch
-    stay independent."""
+def depth_from_stereo_batch(left_u8, right_u8, max_disparity=64, min_disparity=0, p1=4, p2=48, uniqueness=5, lr_check=1, paths=4, speckle=None):
+    """left_u8, right_u8 [n,h,w,c] uint8 cuda tensors -> uint16 [n,h,w] on that device: one ds_stereo_match_u8 call (with paths=8 or a
+    speckle filter: one ds_stereo_match_ex_u8 call; see depth_from_stereo).  Images of a batch stay independent."""
     params = _params(max_disparity, min_disparity, p1, p2, uniqueness, lr_check, 'depth_from_stereo_batch')
-    return _native.stereo_match_u8(left_u8, right_u8, *params)[2]
+    return _match(left_u8, right_u8, params, paths, speckle, 'depth_from_stereo_batch')[2]
+
+
+def filter_speckles(disparity16, valid, size, t, return_sizes=False):
+    """The speckle filter alone, for a disparity map of the caller's: disparity16 int16 [h,w] (any unit; depth_from_stereo's disparity
+    times 16 is sixteenths of a pixel), valid a bool or uint8 mask [h,w], size 1..65535, t 0..65535 in the map's units.  Returns the bool
+    mask of the valid pixels whose connected region (4-neighbours differing by at most t) has more than `size` pixels; with return_sizes
+    also every pixel's region size (int32 [h,w], 0 for an invalid pixel).  Arrays in, arrays out; cuda tensors [n,h,w] (int16 / uint8)
+    in, the tensors of _native.speckle_filter_i16 out."""
+    torch = _native.require_gpu()
+    if torch.is_tensor(disparity16) or torch.is_tensor(valid):
+        out, sizes = _native.speckle_filter_i16(disparity16, valid, size, t, want_sizes=bool(return_sizes))
+        return (out, sizes) if return_sizes else out
+    d, v = np.asarray(disparity16), np.asarray(valid)
+    if d.dtype != np.int16 or d.ndim != 2 or d.size == 0 or v.shape != d.shape or v.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+        raise _native.DepthStereoError("filter_speckles: disparity16 must be a non-empty int16 array [h,w] and valid a bool or uint8 array of "
+                                       "its shape, got %s %s and %s %s" % (d.dtype, d.shape, v.dtype, v.shape))
+    dev = torch.device('cuda', torch.cuda.current_device())
+    out, sizes = _native.speckle_filter_i16(torch.from_numpy(np.array(d, order='C')).to(dev).unsqueeze(0),
+                                            torch.from_numpy(np.array(v != 0, order='C').astype(np.uint8)).to(dev).unsqueeze(0), size, t,
+                                            want_sizes=bool(return_sizes))
+    mask = out[0].cpu().numpy().astype(bool)
+    return (mask, sizes[0].cpu().numpy()) if return_sizes else mask
