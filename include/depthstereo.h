@@ -566,6 +566,76 @@ int ds_speckle_filter_i16(ds_ctx *ctx, const int16_t *disp, const uint8_t *valid
                           int group, uint8_t *valid_out, uint32_t *size_out, void *stream);
 
 /*
+ * ds_mesh_render_u8 -- mesh videos: F views of one coloured triangle mesh through F pinhole cameras, by a triangle rasteriser with a
+ * visibility buffer.  The reference renders its "generate video from mesh" clips through OpenGL; this comment is the definition, and the
+ * only normative text.  It renders the SIMPLE mesh (occluded or stretched) or any other triangle mesh; the inpainted mesh is not built
+ * here.  After the vertex stage everything is an integer, and the depth test is a maximum over 64-bit keys, so the result does not
+ * depend on the order in which anything runs.  `//` is the floor of the exact quotient (all its operands are >= 0 here).
+ * Inputs, all four arrays on the device.  verts [N,3] float64.  colors [N,3] uint8, at any byte address.  faces [M,3] int32.
+ *   cameras [F,6] float64 (tx, ty, tz, f, cx, cy): a translation in the mesh's units, the focal length and the principal point in
+ *   output pixels.  Output size H, W.  Supersampling s in 1..4: the raster has Hs = s H rows of Ws = s W samples.  near: finite, > 0.
+ *   background: three integers 0..255, by value.  M = 0 is legal (faces may then be NULL): every pixel is `background`.
+ *   small_cap in 0..64 and group in 1..F change the launches, never a bit (below).
+ * Vertex (x, y, z) under camera k.  Every float64 operation is rounded on its own (no contraction):
+ *   xc = x - tx;  yc = y - ty;  zc = z - tz.  The vertex is dead unless zc >= near (a NaN fails this).
+ *   sx = cx - (f xc) / zc;  sy = cy - (f yc) / zc: the simple mesh's x = -(u - cx) d / f lands on column u, and an output pixel IS the
+ *   sample at integer coordinates.  Then sx = sx s + (s - 1) 0.5, and sy likewise: pixel u owns the samples s u .. s u + s - 1.
+ *   The vertex is dead unless sx and sy are finite and |sx|, |sy| <= 16384.
+ *   X = rint(16 sx), Y = rint(16 sy): int32 with 4 fraction bits, half to even.
+ *   iz = max(1, floor((near / zc) 2^31)): uint32, 1..2^31; inverse depth, which is linear in screen space.
+ *   A camera row with a NaN or an infinity in any of its six numbers kills every vertex of its frame (tested explicitly: tz = -inf
+ *   would otherwise leave finite coordinates).  The host wrapper refuses such a row beforehand.
+ * Face t with vertices a, b, c is skipped when an index lies outside 0..N-1 (a bad device array cannot address outside the arguments),
+ *   when a vertex is dead (there is no near-plane clipping), when A = (Xb - Xa)(Yc - Ya) - (Yb - Ya)(Xc - Xa) is 0, or when
+ *   max X - min X or max Y - min Y of its vertices exceeds 2048 * 16.
+ *   Coverage of sample (px, py), 0 <= px < Ws, 0 <= py < Hs, with PX = 16 px, PY = 16 py:
+ *     w0 = (Xb - PX)(Yc - PY) - (Yb - PY)(Xc - PX);  w1 = (Xc - PX)(Ya - PY) - (Yc - PY)(Xa - PX);
+ *     with A < 0 (both orientations are drawn): w0 = -w0, w1 = -w1, A = -A;  then w2 = A - w0 - w1.
+ *   The sample is covered when w0, w1, w2 >= 0: edges are inclusive on all sides, overlaps are settled by the key and not by a fill
+ *   rule, so the last row and column of a grid mesh are covered.
+ *   izp = (w0 iz_a + w1 iz_b + w2 iz_c) // A, in 1..2^31.  Inside the bounding box of a kept face every coordinate difference is
+ *   <= 2^15, so |w| <= 2^31 and A <= 2^30; the weights of a covered sample sum to A: the numerator is <= 2^61.  int64 holds everything.
+ * Visibility.  key = (izp << 32) | (0xFFFFFFFF - t).  Keys start at 0 (nothing landed; a hit has izp >= 1); every covered sample takes
+ *   the maximum of the keys offered to it: the nearest face wins, among equal izp the LOWER face index.
+ * Resolve, per output pixel (u, v) of frame k, over its s^2 samples (s u + i, s v + j).  key = 0: the sample is `background`.  Else
+ *   t = 0xFFFFFFFF - (key & 0xFFFFFFFF), w0, w1, w2, A as above, and per channel (w0 c_a + w1 c_b + w2 c_c + A // 2) // A: affine,
+ *   screen-space Gouraud shading -- NOT perspective-correct, which shows on stretched faces.  The pixel is (sum + s^2 // 2) // s^2 per
+ *   channel.
+ * Outputs.  out [F,H,W,3] uint8, at any byte address.  out_hits [F,H,W] uint8: how many of the pixel's samples something landed on,
+ *   0..16; the pointer may be NULL.
+ * Identities.  Let the mesh be the simple mesh of an h x w image with every quad kept (keep_edges), the camera (0, 0, 0, f, cx, cy)
+ *   with the mesh's own intrinsics, and H = h, W = w.  Every vertex lands on X = 16 s u + 8 (s - 1), Y = 16 s v + 8 (s - 1).  With
+ *   s = 1 the output is the image and out_hits = 1 everywhere.  With s > 1 a pixel's samples lie around its vertex, so on the first
+ *   and last row and column some fall outside the mesh, and Gouraud shading mixes the neighbours in: out_hits = n(u, w) n(v, h) with
+ *   n = s inside and (s + 1) // 2 (s odd) or s / 2 (s even) on a first or last index; every channel lies between the minimum and the
+ *   maximum of `background` and the image's 3 x 3 neighbourhood; an image of one colour on a background of that colour comes back.
+ *   Frames are independent of each other and of `group`.  Renumbering the vertices, with the faces remapped, changes nothing.
+ *   The NumPy model is tests/mesh_render_cases.py.
+ * Workspace.  ds_mesh_render_workspace_bytes(N, M, H, W, s) is one frame's share: its keys (8 Hs Ws bytes), a 256-byte counter block,
+ *   its vertex records (16 N bytes: X, Y, iz, live) and its list of large faces (4 M bytes), each rounded to 256 bytes; 0 for sizes the
+ *   entry point refuses.  `workspace` holds `group` shares, 256-byte aligned, any content: frames are rendered `group` at a time, the
+ *   workspace reused in stream order; the memset and the vertex launch write everything a later launch reads.
+ * DS_EINVAL, before any launch: a null pointer other than out_hits (and faces with M = 0); N, F, H or W <= 0, M < 0; s outside 1..4; near not
+ *   finite or <= 0; a background component outside 0..255; small_cap outside 0..64; group outside 1..F; workspace not 256-byte aligned, verts or cameras not 8-byte, faces not 4-byte aligned.
+ *   Then DS_EUNSUPPORTED: Hs or Ws > 16384, N or M >= 2^31, F > 65535, or a share above 2 GiB.  Then DS_EINVAL: an output or the
+ *   workspace overlapping an input or each other.  Asynchronous on `stream`, no allocation, safe under graph capture.  Per group one
+ *   memset (keys and counters) and four launches: vertices; faces (a thread per face walks a bounding box of at most small_cap samples
+ *   itself and appends the others to the frame's list); the listed faces (a fixed grid, one wave per face, the count read from device
+ *   memory; small_cap = 0 sends every face with a non-empty box here); resolve.  Every loop is bounded (small_cap samples per thread,
+ *   2048^2 per wave, s^2 per pixel); no kernel waits for another workgroup.  No kernel-timer kind.
+ * ds_mesh_render_stages_u8 is the same call restricted to the launches named by `stages`, a sum of 1 = memset, 2 = vertices, 4 = faces,
+ *   8 = listed faces, 16 = resolve (1..31; 31 is ds_mesh_render_u8): tools/mesh_render_ab.py times each with it.  A partial run leaves
+ *   partial results.
+ */
+size_t ds_mesh_render_workspace_bytes(int64_t N, int64_t M, int H, int W, int s);
+int ds_mesh_render_u8(ds_ctx *ctx, const double *verts, const uint8_t *colors, const int32_t *faces, int64_t N, int64_t M,
+                      const double *cameras, int F, int H, int W, int s, double near, int bg_r, int bg_g, int bg_b, int small_cap,
+                      void *workspace, int group, uint8_t *out, uint8_t *out_hits, void *stream);
+int ds_mesh_render_stages_u8(ds_ctx *ctx, const double *verts, const uint8_t *colors, const int32_t *faces, int64_t N, int64_t M,
+                             const double *cameras, int F, int H, int W, int s, double near, int bg_r, int bg_g, int bg_b, int small_cap,
+                             void *workspace, int group, uint8_t *out, uint8_t *out_hits, int stages, void *stream);
+
+/*
  * ds_frame_luma_hist -- per-frame luma histograms of a uint8 clip: the input of video mode's scene-cut detector (the reference
  * leaves cut detection as a TODO, src/video_mode.py:114, and has no implementation; this comment is the definition).
  * frames [n,h,w,c] uint8, dense, ANY byte alignment -> hist [n,256] uint32: hist[f][v] = the number of pixels of frame f with Y == v.

@@ -27,7 +27,7 @@ EXPORTS = [
     "ds_row_stats", "ds_linear_ln", "ds_linear_vt_ln", "ds_gconv3x3_nhwc_f32", "ds_add_relu_f32", "ds_bias_act_f32", "ds_relu_cat_f32",
     "ds_dwconv_nhwc", "ds_resize_lanczos", "ds_custom_depth_to_f64", "ds_conv3x3_nhwc_circular", "ds_dpt_head_tail_circular",
     "ds_normalmap_wrap", "ds_normalmap_f64_wrap", "ds_normalmap_gradient_f32_wrap", "ds_normalmap_gradient_f16_wrap", "ds_normalmap_gradient_blur_f32_wrap",
-    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_aomap_u16", "ds_lensblur_u8", "ds_parallax_u8", "ds_autostereogram_u8", "ds_autostereogram_rounds_u8", "ds_stereo_match_workspace_bytes", "ds_stereo_match_u8", "ds_stereo_match_stages_u8", "ds_stereo_match_ex_workspace_bytes", "ds_stereo_match_ex_u8", "ds_stereo_match_ex_stages_u8", "ds_speckle_filter_workspace_bytes", "ds_speckle_filter_i16", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
+    "ds_bilateral_u16", "ds_joint_bilateral_u16", "ds_sparse_bilateral_f32", "ds_sparse_bilateral_jump_f32", "ds_aomap_u16", "ds_lensblur_u8", "ds_parallax_u8", "ds_mesh_render_workspace_bytes", "ds_mesh_render_u8", "ds_mesh_render_stages_u8", "ds_autostereogram_u8", "ds_autostereogram_rounds_u8", "ds_stereo_match_workspace_bytes", "ds_stereo_match_u8", "ds_stereo_match_stages_u8", "ds_stereo_match_ex_workspace_bytes", "ds_stereo_match_ex_u8", "ds_stereo_match_ex_stages_u8", "ds_speckle_filter_workspace_bytes", "ds_speckle_filter_i16", "ds_frame_luma_hist", "ds_temporal_smooth5_f32", "ds_temporal_joint_bilateral_u16",
     "ds_preprocess_bicubic_rows", "ds_tokens_fixup", "ds_upsample_bicubic_to_f32", "ds_im2col3x3_s2_nhwc", "ds_dpt_head_front",
 ]
 
@@ -92,6 +92,10 @@ def lib():
             L.ds_aomap_u16.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, cd, cd, ci, ci, vp, vp, vp]
             L.ds_lensblur_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]
             L.ds_parallax_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, ci, vp, vp, vp, vp]
+            L.ds_mesh_render_workspace_bytes.argtypes = [i64, i64, ci, ci, ci]
+            L.ds_mesh_render_workspace_bytes.restype = ctypes.c_size_t
+            L.ds_mesh_render_u8.argtypes = [vp, vp, vp, vp, i64, i64, vp, ci, ci, ci, ci, cd, ci, ci, ci, ci, vp, ci, vp, vp, vp]
+            L.ds_mesh_render_stages_u8.argtypes = [vp, vp, vp, vp, i64, i64, vp, ci, ci, ci, ci, cd, ci, ci, ci, ci, vp, ci, vp, vp, ci, vp]
             L.ds_autostereogram_u8.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ctypes.c_uint32, vp, ci, ci, ci, vp, vp]
             L.ds_autostereogram_rounds_u8.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ctypes.c_uint32, vp, ci, ci, ci, vp, vp, vp]
             L.ds_stereo_match_workspace_bytes.argtypes = [ci, ci, ci]
@@ -1019,6 +1023,156 @@ def parallax_u8(image_u8, depth_u16, poses, focus, fill, invert=False, want_mask
             if mask is not None:
                 mask[:, k0:k1].copy_(part_mask)
     return (out, mask) if want_mask else out
+
+
+# ---- mesh videos (csrc/ds_mesh_render.hip; public interface: src/mesh_render.py) ------------------------------------------------------
+MESH_RENDER_TRAJS = ('straight-line', 'double-straight-line', 'circle')
+MESH_RENDER_MAX_FRAMES = 1024
+MESH_RENDER_MAX_SHIFT = 1.0e6        # mesh units; anything finite would do, this keeps the arithmetic of a path far from overflow
+MESH_RENDER_MAX_SSAA = 4
+MESH_RENDER_MAX_SIDE = 16384
+MESH_RENDER_CAP_MAX = 64
+MESH_RENDER_SMALL_CAP = 16           # boxes of up to this many samples are walked by their face's own thread
+MESH_RENDER_WS_BYTES = 1 << 30       # the workspace mesh_render_u8 allocates when the caller names no group
+MESH_RENDER_DEFAULTS = (False, 1, True)              # dolly, ssaa, keep_edges
+
+
+def _as_flag(v):
+    if isinstance(v, (bool, np.bool_)):
+        return bool(v)
+    raise TypeError
+
+
+def mesh_render_params(p):
+    """(traj, frames, shift_x, shift_y, shift_z[, dolly[, ssaa[, keep_edges]]]) as (str, int, float, float, float, bool, int, bool), or
+    ValueError; what is left out takes (False, 1, True).  traj: 'straight-line', 'double-straight-line' or 'circle' (the reference's
+    trajectory kinds).  frames: an integer in 1..1024.  shift: three finite numbers, the camera translation in the mesh's units.  dolly,
+    keep_edges: bools.  ssaa: an integer in 1..4.  A bool is no integer, a string no number.  Pure Python (the funnel checks its option
+    with it before any device work)."""
+    usage = "(traj, frames, shift_x, shift_y, shift_z[, dolly[, ssaa[, keep_edges]]])"
+    try:
+        if isinstance(p, (str, bytes)):
+            raise TypeError
+        q = tuple(p)
+        if len(q) not in (5, 6, 7, 8):
+            raise TypeError
+    except TypeError:
+        raise ValueError("mesh_video must be %s, got %r" % (usage, p)) from None
+    if not isinstance(q[0], str) or q[0] not in MESH_RENDER_TRAJS:
+        raise ValueError("mesh_video: traj must be one of %r, got %r" % (MESH_RENDER_TRAJS, q[0]))
+    try:
+        if isinstance(q[1], (str, bytes)):
+            raise TypeError
+        frames, ok = _as_int(q[1])
+        if not (ok and 1 <= frames <= MESH_RENDER_MAX_FRAMES):
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("mesh_video: frames must be an integer in 1..%d, got %r" % (MESH_RENDER_MAX_FRAMES, q[1])) from None
+    try:
+        shift = tuple(_as_float(v, MESH_RENDER_MAX_SHIFT) for v in q[2:5])
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("mesh_video: shift must be three numbers with |shift| <= %g, got %r" % (MESH_RENDER_MAX_SHIFT, q[2:5])) from None
+    dolly, ssaa, keep_edges = MESH_RENDER_DEFAULTS
+    try:
+        if len(q) > 5:
+            dolly = _as_flag(q[5])
+        if len(q) > 7:
+            keep_edges = _as_flag(q[7])
+    except TypeError:
+        raise ValueError("mesh_video: dolly and keep_edges must be bools, got %r" % (q[5:6] + q[7:8],)) from None
+    if len(q) > 6:
+        try:
+            if isinstance(q[6], (str, bytes)):
+                raise TypeError
+            ssaa, ok = _as_int(q[6])
+            if not (ok and 1 <= ssaa <= MESH_RENDER_MAX_SSAA):
+                raise ValueError
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("mesh_video: ssaa must be an integer in 1..%d, got %r" % (MESH_RENDER_MAX_SSAA, q[6])) from None
+    return (q[0], frames) + shift + (dolly, ssaa, keep_edges)
+
+
+def mesh_render_workspace_bytes(N, M, H, W, s):
+    """ds_mesh_render_workspace_bytes: one frame's share of the workspace, 0 for sizes the entry point refuses."""
+    return int(lib().ds_mesh_render_workspace_bytes(int(N), int(M), int(H), int(W), int(s)))
+
+
+def mesh_render_u8(verts, colors, faces, cameras, H, W, s=1, near=0.05, background=(0, 0, 0), small_cap=None, group=None, want_hits=False,
+                   stages=None):
+    """F views of a coloured triangle mesh (ds_mesh_render_u8: the definition is in include/depthstereo.h).  verts float64 [N,3], colors
+    uint8 [N,3], faces int32 [M,3] (M = 0 is legal): cuda tensors of one device.  cameras: a HOST array [F,6] of finite numbers (tx, ty,
+    tz, f, cx, cy); a NaN or an infinity is refused here, before the kernel would kill the frame.  H, W: the output size; s: 1..4
+    samples per pixel side; near > 0; background: three integers 0..255.  small_cap 0..64 (None: MESH_RENDER_SMALL_CAP) and group 1..F
+    (None: the largest whose workspace stays within MESH_RENDER_WS_BYTES) change launches, never a bit.  Returns uint8 [F,H,W,3], with
+    want_hits (that, uint8 [F,H,W]).  The workspace comes from torch's allocator.  stages: ds_mesh_render_stages_u8 (timing only)."""
+    torch = require_gpu()
+    who = "mesh_render_u8"
+    for name, t, dt, cols in (("verts", verts, torch.float64, 3), ("colors", colors, torch.uint8, 3), ("faces", faces, torch.int32, 3)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.dim() == 2 and t.shape[1] == cols):
+            raise DepthStereoError("%s: %s must be a %s cuda tensor [*,%d], got %s %s"
+                                   % (who, name, str(dt).replace("torch.", ""), cols, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    if not (verts.device == colors.device == faces.device) or verts.shape[0] != colors.shape[0] or verts.shape[0] == 0:
+        raise DepthStereoError("%s: verts %s and colors %s must have one length >= 1, and all arrays one device"
+                               % (who, tuple(verts.shape), tuple(colors.shape)))
+    cams = None if torch.is_tensor(cameras) or isinstance(cameras, (str, bytes)) or cameras is None else np.asarray(cameras)
+    if (cams is None or cams.dtype.kind not in 'iuf' or cams.ndim != 2 or cams.shape[1] != 6 or not 1 <= cams.shape[0] <= 65535
+            or not np.isfinite(cams.astype(np.float64)).all()):
+        raise DepthStereoError("%s: cameras must be a host array [F,6] of finite numbers with 1 <= F <= 65535, got %r" % (who, cameras))
+    ints = []
+    for name, v, lo, hi in (("H", H, 1, MESH_RENDER_MAX_SIDE), ("W", W, 1, MESH_RENDER_MAX_SIDE), ("s", s, 1, MESH_RENDER_MAX_SSAA),
+                            ("small_cap", MESH_RENDER_SMALL_CAP if small_cap is None else small_cap, 0, MESH_RENDER_CAP_MAX)):
+        try:
+            if isinstance(v, (str, bytes)):
+                raise TypeError
+            iv, ok = _as_int(v)
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not (ok and lo <= iv <= hi):
+            raise DepthStereoError("%s: %s must be an integer in %d..%d, got %r" % (who, name, lo, hi, v))
+        ints.append(iv)
+    H, W, s, small_cap = ints
+    try:
+        near = _as_float(near, 1.0e300)
+        if not near > 0.0:
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise DepthStereoError("%s: near must be a finite number > 0, got %r" % (who, near)) from None
+    try:
+        bg = [_as_int(v) for v in background]
+        if len(bg) != 3 or not all(ok and not isinstance(v, (bool, np.bool_)) and 0 <= iv <= 255 for (iv, ok), v in zip(bg, background)):
+            raise ValueError
+        bg = [iv for iv, _ in bg]
+    except (TypeError, ValueError, OverflowError):
+        raise DepthStereoError("%s: background must be three integers in 0..255, got %r" % (who, background)) from None
+    N, M, F = verts.shape[0], faces.shape[0], cams.shape[0]
+    share = mesh_render_workspace_bytes(N, M, H, W, s)
+    if share == 0:
+        raise DepthStereoError("%s: s H and s W must be <= %d and one frame's workspace <= 2 GiB, got N=%d M=%d H=%d W=%d s=%d"
+                               % (who, MESH_RENDER_MAX_SIDE, N, M, H, W, s))
+    if group is None:
+        group = max(1, min(F, MESH_RENDER_WS_BYTES // share))
+    else:
+        try:
+            group, ok = _as_int(group)
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not (ok and 1 <= group <= F):
+            raise DepthStereoError("%s: group must be an integer in 1..F = %d, got %r" % (who, F, group))
+    verts, colors, faces = verts.contiguous(), colors.contiguous(), faces.contiguous()
+    dev = verts.device
+    cams_t = torch.from_numpy(np.array(cams, dtype=np.float64, order="C")).to(dev)
+    out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+    hits = torch.empty((F, H, W), dtype=torch.uint8, device=dev) if want_hits else None
+    workspace = torch.empty((group * share,), dtype=torch.uint8, device=dev)              # (torch's blocks are 512-byte aligned)
+    args = (ctx_for(_dev_index(verts)), verts.data_ptr(), colors.data_ptr(), faces.data_ptr() if M else None, N, M, cams_t.data_ptr(), F, H, W, s,
+            near, bg[0], bg[1], bg[2], small_cap, workspace.data_ptr(), group, out.data_ptr(), hits.data_ptr() if hits is not None else None)
+    if stages is None:
+        CALLS["ds_mesh_render_u8"] += 1
+        _check(lib().ds_mesh_render_u8(*args, _stream(verts)))
+    else:
+        CALLS["ds_mesh_render_stages_u8"] += 1
+        _check(lib().ds_mesh_render_stages_u8(*args, int(stages), _stream(verts)))
+    return (out, hits) if want_hits else out
 
 
 # ---- autostereograms from depth (csrc/ds_autostereogram.hip; public interface: src/autostereogram_generation.py) ---------------------

@@ -865,7 +865,7 @@ def _render_unit(g, j):
     return [_run_task(g, j, t) for t in _unit_tasks(g, j)]
 
 
-def _emit_group(g, outpath, inp, device, stats):
+def _emit_group(g, outpath, inp, device, stats, mesh_video=None):
     """Yield a finished group's results image by image in the reference's order (:208-306).  The pinned buffers are reused
     two groups later, so every result is copied out of them (PIL owns its pixels); the conversions were handed to the render
     pool when the group was launched (_unit_tasks: each waits for its own chunk of copies), the generator hands out what is done."""
@@ -889,6 +889,14 @@ def _emit_group(g, outpath, inp, device, stats):
                 yield count, kind, res
             if g.get("stereo_error") is not None:
                 raise g["stereo_error"]
+            if mesh_video is not None:                                                               # ops['mesh_video'] (src/mesh_render.py)
+                from . import mesh_generation as mg, mesh_render
+                mt = inp[go.MODEL_TYPE]
+                depthi = mg.mesh_depth(g["mesh_source"][j], mt if isinstance(mt, int) else -1, bool(inp[go.BOOST]), g["custom"])
+                rgb_t = torch.from_numpy(np.array(image.convert('RGB'), dtype=np.uint8, order='C')).to(device)
+                clip = mesh_render._render_grid(torch, rgb_t, depthi, mesh_video[0], mesh_video[1], mesh_video[2:5], mesh_video[5],
+                                                mesh_video[6], mesh_video[7], depthi.shape[0], depthi.shape[1])
+                yield count, 'mesh_video', [_to_pil(f) for f in clip.cpu().numpy()]
             if inp[go.GEN_SIMPLE_MESH]:                                                              # :277-306
                 from . import mesh_generation as mg
                 mt = inp[go.MODEL_TYPE]              # callers pass the numeric id; the option's default is a display name
@@ -999,6 +1007,14 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
     # checked here before any device work; together with inputdepthmaps it is a ValueError.  Beside it, and only beside it,
     # ops['stereo_paths']: 4 | 8 (8 adds the diagonal paths) and ops['stereo_speckle']: (size, range), the speckle filter between the
     # checks and the fill (ds_stereo_match_ex_u8); absent, the matching is ds_stereo_match_u8's, launch for launch.
+    # ops['mesh_video'] (the reference's "generate video from mesh", for the SIMPLE mesh -- not the inpainted one): (traj, frames, shift_x,
+    # shift_y, shift_z[, dolly[, ssaa[, keep_edges]]]) = the planar simple mesh of the image, built from mesh_source through mesh_depth
+    # exactly as GEN_SIMPLE_MESH builds it, rendered along a camera path (src/mesh_render.py) and yielded as (i, 'mesh_video', [frames])
+    # after 'autostereogram' and before 'simple_mesh'.  Absent / None = off, and then the call makes the launches it always made.  An
+    # option of THIS call, checked here before any device work.
+    mesh_video = ops.get('mesh_video')
+    if mesh_video is not None:
+        mesh_video = _native.mesh_render_params(mesh_video)
     stereo_input = ops.get('stereo_input')
     if stereo_input is not None:
         from . import stereo_matching
@@ -1016,7 +1032,7 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
         raise ValueError("ops['stereo_paths'] and ops['stereo_speckle'] are options of ops['stereo_input'] and need it")
     model_holder.update_settings(**{k: v for k, v in ops.items()
                                     if k not in ('normalmap_wrap', 'normalmap_bilateral', 'depth_refine', 'depth_refine_wrap', 'aomap',
-                                                 'aomap_wrap', 'lensblur', 'parallax', 'autostereogram', 'stereo_input', 'stereo_paths',
+                                                 'aomap_wrap', 'lensblur', 'parallax', 'autostereogram', 'mesh_video', 'stereo_input', 'stereo_paths',
                                                  'stereo_speckle')})
 
     torch = _native.require_gpu()        # the hot path has no CPU implementation, whatever COMPUTE_DEVICE says
@@ -1054,12 +1070,12 @@ def core_generation_funnel(outpath, inputimages, inputdepthmaps, inputnames, inp
             except Exception as e:          # noqa: BLE001 -- re-raised below, after the results that precede it
                 launched, failure = None, e
             if pending is not None:
-                yield from _emit_group(pending, outpath, inp, device, stats)
+                yield from _emit_group(pending, outpath, inp, device, stats, mesh_video)
             if failure is not None:
                 raise failure
             pending = launched
         if pending is not None:
-            yield from _emit_group(pending, outpath, inp, device, stats)
+            yield from _emit_group(pending, outpath, inp, device, stats, mesh_video)
         stats["groups"] = len(groups)
         stats["finished"] = True
     except Exception as e:
